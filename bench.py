@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the ContextUnet DDPM hot path on MI355X (driver contract, one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sample-steps S] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--sample-steps S] [--no-cpu] [--no-extra]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
+
+A plain run sets up, warms up, times the K train steps, writes their outputs if --dump-outputs is given and prints
+the result line (`value`, `ms_per_step`, ...).  Every other leg below runs only with --full.
 
 Metric (BASELINE.json): train-step images/s + T=1500 sample images/s, 64x64x1, bs=256 per GPU.
   value   = whole-job train-step throughput: N * 256 images / (max over ranks of the time of K steps)
             one step = Philox noise/t + perturb + ContextUnet fwd (train BN) + mse + bwd + Adam
             (+ bucketed RCCL gradient all-reduce when N > 1), n_feat=128, 6 params, fp32, synthetic data.
+--full adds:
   sample  = T=1500 reverse diffusion of 256 images per GPU (w=0, hipGraph-captured steps, on-device
             snapshots): images / wall time; replicas only when N > 1 (no collective).
             + CFG (w=1, 3: cond + uncond halves in one batched forward) over --cfg-sample-steps, extrapolated.
@@ -321,9 +326,40 @@ def sample_rate(model, T: int, n: int, w: float, steps: int, rank: int, barrier,
     return dts / S * 1e3, S
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+DUMP_TENSOR_CAP = 1 << 20               # elements kept of one tensor (halved until the whole dump fits the budget)
+
+
+def dump_outputs(trainer, out_dir: str):
+    """--dump-outputs: what the last timed Trainer.step left with its caller, as float32 <name>.npy files in out_dir:
+    loss (the step's return value), param.<name> (every parameter after the step's Adam update), grad.<name> (its
+    gradient, Trainer.grads) and bn_running_stats (the BatchNorm running means / variances, Trainer.bnflat).  A tensor of
+    more than `cap` elements is written as a fixed sample: the flattened tensor at sorted indices drawn from
+    numpy's RandomState seeded by the tensor's position in the parameter list, so two builds write the same
+    elements; cap is DUMP_TENSOR_CAP, halved until the files hold at most 64 MB."""
+    import numpy as np
+    named = [("loss", trainer.loss), ("bn_running_stats", trainer.bnflat)]
+    for n in trainer.views:
+        named.append(("param." + n, trainer.views[n]))
+        named.append(("grad." + n, trainer.grads[n]))
+    cap = DUMP_TENSOR_CAP
+    while sum(min(t.numel(), cap) for _, t in named) * 4 > DUMP_BUDGET_BYTES - 256 * len(named):   # 256: .npy header
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    if trainer.loss.is_cuda:
+        torch.cuda.synchronize()
+    for i, (name, t) in enumerate(named):
+        a = t.detach().reshape(-1)
+        if a.numel() > cap:
+            idx = np.sort(np.random.RandomState(i // 2).randint(0, a.numel(), cap))   # a param and its grad: same idx
+            a = a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 def train_rate(nf: int, H: int, T: int, B: int, math: str, steps: int, warmup: int, rank: int, barrier,
-               use_graph: bool = True, dist=None, conv_probe: bool = False):
-    """Train steps/s of a fresh seeded ContextUnet on synthetic data -> (model, ms/step, final loss[, conv timing])."""
+               use_graph: bool = True, dist=None, conv_probe: bool = False, dump_dir=None):
+    """Train steps/s of a fresh seeded ContextUnet on synthetic data -> (model, ms/step, final loss[, conv timing]).
+    dump_dir: write the last timed step's outputs there (dump_outputs), before anything else runs on the trainer."""
     from cdm_amd import ContextUnet, Trainer
     torch.manual_seed(0)
     model = ContextUnet(1, nf, NCF, H, shortcut_source="device", conv_math=math).cuda()
@@ -350,6 +386,8 @@ def train_rate(nf: int, H: int, T: int, B: int, math: str, steps: int, warmup: i
         tt = torch.tensor([dt], device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if dump_dir:
+        dump_outputs(trainer, dump_dir)
     conv = time_dominant_conv_in_step(trainer, x0, c) if conv_probe else None
     del trainer
     model.eval()
@@ -572,6 +610,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients, BatchNorm "
+                         "running statistics; rank 0) as DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: sampling (w=0 and CFG), the dominant conv's roofline, the reference's "
+                         "logged workloads, configs C4 / C5, the CPU baseline (--sample-steps, --sample-batch, --cfg-sample-steps, "
+                         "--extra-sample-steps, --c5-batch, --no-extra, --no-cpu and --cpu-threads shape these legs)")
     ap.add_argument("--sample-steps", type=int, default=T, help="sampling steps actually run (T=1500 = full)")
     ap.add_argument("--sample-batch", type=int, default=256)
     ap.add_argument("--cfg-sample-steps", type=int, default=T,
@@ -625,12 +670,45 @@ def main():
         torch.cuda.synchronize()
 
     B = args.batch
-    model, ms_step, loss, (conv_ms, conv_n) = train_rate(NF, H, T, B, args.conv_math, args.steps, args.warmup, rank,
-                                                         barrier, use_graph=not args.no_graph, dist=dist,
-                                                         conv_probe=True)
+    res = train_rate(NF, H, T, B, args.conv_math, args.steps, args.warmup, rank, barrier, use_graph=not args.no_graph,
+                     dist=dist, conv_probe=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
+    model, ms_step, loss = res[:3]
     train_ips = world * B / (ms_step * 1e-3)
     c2_steps = step_stats(getattr(train_rate, "last_step_ms", None))
     _progress(f"C2 train {ms_step:.3f} ms/step")
+    head = {
+        "metric": METRIC,
+        "value": round(train_ips, 3),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic",
+        "config": {"workload": "ContextUnet DDPM train step (fwd+bwd+Adam), n_feat=128, 6 params, 64x64x1, "
+                               "T=1500, train-mode BatchNorm",
+                   "batch_per_gpu": B, "global_batch": B * world, "n_feat": NF, "n_cfeat": NCF, "T": T,
+                   "parallelism": f"dp{world}", "conv_math": args.conv_math},
+    }
+    tail = {
+        "train_tflops_per_gpu": round(3 * FWD_GFLOP_PER_IMG * B / (ms_step * 1e-3) / 1e3, 2),
+        "train_step_stats": c2_steps,
+        "final_loss": loss,
+    }
+    if not args.full:                   # the plain run: the train-step figure alone
+        del model
+        if rank == 0:
+            wp = whole_path_rooflines(args.conv_math, B, ms_step, args.sample_batch, {})
+            print(json.dumps({**head, "full": False, **tail, "whole_path_roofline": wp}), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    conv_ms, conv_n = res[3]
 
     # ---------------- sampling (replicas) ----------------
     n = args.sample_batch
@@ -660,22 +738,8 @@ def main():
     out = None
     if rank == 0:
         out = {
-            "metric": METRIC,
-            "value": round(train_ips, 3),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic",
-            "config": {"workload": "ContextUnet DDPM train step (fwd+bwd+Adam), n_feat=128, 6 params, 64x64x1, "
-                                   "T=1500, train-mode BatchNorm",
-                       "batch_per_gpu": B, "global_batch": B * world, "n_feat": NF, "n_cfeat": NCF, "T": T,
-                       "parallelism": f"dp{world}", "conv_math": args.conv_math},
+            **head,
+            "full": True,
             "sample": {"img_per_s": round(sample_ips, 4), "T": T, "steps_run": S, "extrapolated": S < T,
                        "n_per_gpu": n, "guide_w": 0.0, "ms_per_denoise_step": round(sms, 3),
                        "scaling": "replicas", "cfg": cfg},
@@ -697,10 +761,8 @@ def main():
                                            f"bf16/fp16 MFMA dense {PEAK_BF16_TFLOPS:.0f} / "
                                            f"{CONV_MATH_INFO[args.conv_math][0]} products per fp32 MAC"),
                          "vs_fp32_mfma_peak": round(conv_tflops / PEAK_FP32_TFLOPS, 4)},
-            "train_tflops_per_gpu": round(3 * FWD_GFLOP_PER_IMG * B / (ms_step * 1e-3) / 1e3, 2),
-            "train_step_stats": c2_steps,
+            **tail,
             "whole_path_roofline": wp,
-            "final_loss": loss,
         }
         out["sample"]["roofline"] = {k[len("sample_"):]: v for k, v in wp.items() if k.startswith("sample_")}
         if extra:

@@ -54,6 +54,36 @@ def test_whole_path_rooflines_and_step_stats():
     assert b.step_stats([]) is None
 
 
+def test_dump_outputs_sampling_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files of the loss, the BatchNorm running statistics and every parameter / gradient; a
+    tensor above the cap is a fixed sample (the same elements on every call, the same indices for a parameter and its
+    gradient), and the cap halves until the files fit the byte budget."""
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    big = torch.arange(5000, dtype=torch.float32)
+    tr = types.SimpleNamespace(loss=torch.tensor([0.25]), bnflat=torch.ones(6, dtype=torch.float32),
+                               views={"w": big.reshape(50, 100), "b": torch.tensor([1.0, 2.0])},
+                               grads={"w": -big.reshape(50, 100), "b": torch.tensor([3.0, 4.0])})
+    monkeypatch.setattr(b, "DUMP_TENSOR_CAP", 1024)
+    b.dump_outputs(tr, str(tmp_path / "a"))
+    b.dump_outputs(tr, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_running_stats.npy", "grad.b.npy", "grad.w.npy", "loss.npy", "param.b.npy", "param.w.npy"]
+    A = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert A[n].dtype == np.float32 and np.array_equal(A[n], np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(A["loss.npy"], [0.25]) and np.array_equal(A["param.b.npy"], [1.0, 2.0])
+    w = A["param.w.npy"]
+    assert w.shape == (1024,) and np.all(np.diff(w) >= 0) and len(np.unique(w)) > 900 and w.max() > 4900
+    assert np.array_equal(A["grad.w.npy"], -w)
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 6 * 256 + 4 * (2 * 300 + 11))    # fits at cap 256, not at 512
+    b.dump_outputs(tr, str(tmp_path / "c"))
+    assert np.load(tmp_path / "c" / "param.w.npy").shape == (256,)
+    assert sum(os.path.getsize(tmp_path / "c" / n) for n in names) <= b.DUMP_BUDGET_BYTES
+
+
 def _run_bench(*args, env_extra=None, timeout=240):
     import json
     import subprocess
