@@ -37,56 +37,17 @@ static int conv3x3_fwd_split(const float* x, int N, int H, int W, int Cin, int l
         MkRowK<LA>{LA{x, H, W, Cin, ldx, M, K}, amax_x}, mb, ep, M, Cout, K, 1, nterm, st);
 }
 
-// timing ablations of the h3 LDS-halo kernel (W = H = 64, kc = 16; tools/conv_ablation.py only)
+// the tiles-per-block hook of the shipped h3 LDS-halo kernel (W = H = 64, kc = 16; tests): abl = 1 | tpb << 16 launches
+// the dispatched instantiation with tpb tiles per block (0 -> 1) instead of the halo_tpb policy; any other low 16 bits
+// (the retired timing-ablation masks) are an error and launch nothing
 CDM_API int cdm_conv3x3_halo_ablate(int abl, const float* x, int N, int H, int Cin, int ldx, const void* wx,
                                     const float* amax_x, const float* amax_w, float* y, int ldy, int Cout,
                                     void* stream) {
-    if (H != 64 || Cin % 16 || ldx % 4) return (int)hipErrorInvalidValue;
-    const int M = N * H * 64, mtiles = M / HBM_;
-    if ((unsigned long long)M * (unsigned)ldx * 4ull >= (1ull << 32)) return (int)hipErrorInvalidValue;
-    const int tpb = (abl >> 16) > 0 ? (abl >> 16) : 1;   // tiles per block in the high bits (0 -> 1)
-    abl &= 0xffff;
+    if ((abl & 0xffff) != 1 || H != 64 || Cin % 16 || ldx % 4) return (int)hipErrorInvalidValue;
+    const int M = N * H * 64, tpb = (abl >> 16) > 0 ? (abl >> 16) : 1;
     const EpiStoreW<4> eh{y, ldy, 0, nullptr, Cout, 0, nullptr, 0, M, Cout};
-    const __bf16* b = reinterpret_cast<const __bf16*>(wx);
-    dim3 grid((mtiles + tpb - 1) / tpb, (Cout + GBN - 1) / GBN, 1);
-    hipStream_t s = S(stream);
-#define CDM_ABL(A) hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, 64, EpiStoreW<4>, true, A>), grid, dim3(HTHREADS), 0, \
-                                      s, x, H, Cin, ldx, b, Cout, amax_x, amax_w, eh, PreNone{}, mtiles, tpb)
-    switch (abl) {
-        case 0: CDM_ABL(0); break;
-        case 1: CDM_ABL(1); break;
-        case 2: CDM_ABL(2); break;
-        case 4: CDM_ABL(4); break;
-        case 8: CDM_ABL(8); break;
-        case 12: CDM_ABL(12); break;
-        case 14: CDM_ABL(14); break;
-        case 16: CDM_ABL(16); break;
-        case 32: CDM_ABL(32); break;
-        case 17: CDM_ABL(17); break;
-        case 3: CDM_ABL(3); break;
-        case 5: CDM_ABL(5); break;
-        case 9: CDM_ABL(9); break;
-        case 13: CDM_ABL(13); break;
-        case 21: CDM_ABL(21); break;
-        case 25: CDM_ABL(25); break;
-        case 29: CDM_ABL(29); break;
-        case 33: CDM_ABL(33); break;
-        case 45: CDM_ABL(45); break;
-        case 16385: CDM_ABL(16385); break;
-        case 16445: CDM_ABL(16445); break;
-        case 60: CDM_ABL(60); break;
-        case 61: CDM_ABL(61); break;
-        case 62: CDM_ABL(62); break;
-        case 65: CDM_ABL(65); break;
-        case 129: CDM_ABL(129); break;
-        case 257: CDM_ABL(257); break;
-        case 513: CDM_ABL(513); break;
-        case 769: CDM_ABL(769); break;
-        case 1025: CDM_ABL(1025); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CDM_ABL
-    return cdm_status();
+    return launch_conv_halo<64>(x, N, H, Cin, ldx, reinterpret_cast<const __bf16*>(wx), Cout, amax_x, amax_w, eh, NT_H3,
+                                S(stream), PreNone{}, tpb);
 }
 
 CDM_API int cdm_conv3x3_fwd_x3(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx3,

@@ -455,164 +455,10 @@ struct EpiStoreW {  // y[m*ldy + n] (+)= acc + bias[n % bias_mod]; optional per-
             }
         }
     }
-
-    // tall wave tiles (conv3x3_halo_x3_kernel, ABL 8192; 2 waves along M of the 256-row block): the wave holds rows
-    // mw..mw+127 (4 row blocks of 32) x columns nw..nw+63, i.e. exactly one 128-row stats tile, written directly
-    __device__ __forceinline__ void tall(f32x16 (&acc)[4][2], int mw, int nw, int lane, int wm, int wn, float* scratch,
-                                         int tid) const {
-        static_assert(WM == 4, "tall tiles: a 256-row block");
-        constexpr int NWM = 2;   // waves along M
-        OT* yz = y + (long long)blockIdx.z * zstride;
-        // column sums per half (row blocks 0-1, 2-3), added as the 64 x 64 form adds its two waves: identical stats
-        float cs[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, cq[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-        float cmx[2] = {-INFINITY, -INFINITY}, cmn[2] = {INFINITY, INFINITY};
-        float am = 0.f;
-        const bool relu = flags & EPI_RELU;
-        const bool accum = flags & EPI_ACCUM;
-        if (mw + 128 <= M && (nw - wn * 64) + GBN <= N) {
-            float bj[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bj[j] = bias ? bias[(nw + 32 * j + (lane & 31)) % bias_mod] : 0.f;
-            if constexpr (ACC) {   // the load-ahead accumulate (see operator())
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        float old[16];
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int m = mw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                            old[r] = Act<OT>::load(yz + (long long)m * ldy + nw + 32 * j + (lane & 31));
-                        }
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int m = mw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                            const int n = nw + 32 * j + (lane & 31);
-                            float v = acc[i][j][r] + bj[j] + old[r];
-                            if (relu) v = relu_f(v);
-                            v = Act<OT>::round(v);
-                            Act<OT>::store(yz + (long long)m * ldy + n, v);
-                            cs[i >> 1][j] += v; cq[i >> 1][j] += v * v;
-                            am = fmaxf(am, fabsf(v));
-                            cmx[j] = fmaxf(cmx[j], v); cmn[j] = fminf(cmn[j], v);
-                        }
-                    }
-            } else {
-                CDM_FOR_ACC_N(4, {
-                    float v = acc[i][j][r] + bj[j];
-                    if (accum) v += Act<OT>::load(yz + (long long)m * ldy + n);
-                    if (relu) v = relu_f(v);
-                    v = Act<OT>::round(v);
-                    Act<OT>::store(yz + (long long)m * ldy + n, v);
-                    cs[i >> 1][j] += v; cq[i >> 1][j] += v * v;
-                    am = fmaxf(am, fabsf(v));
-                    cmx[j] = fmaxf(cmx[j], v); cmn[j] = fminf(cmn[j], v);
-                })
-            }
-        } else {
-            CDM_FOR_ACC_N(4, {
-                if (m < M && n < N) {
-                    float v = acc[i][j][r];
-                    if (bias) v += bias[n % bias_mod];
-                    OT* p = yz + (long long)m * ldy + n;
-                    if (accum) v += Act<OT>::load(p);
-                    if (relu) v = relu_f(v);
-                    v = Act<OT>::round(v);
-                    Act<OT>::store(p, v);
-                    cs[i >> 1][j] += v; cq[i >> 1][j] += v * v;
-                    am = fmaxf(am, fabsf(v));
-                    cmx[j] = fmaxf(cmx[j], v); cmn[j] = fminf(cmn[j], v);
-                }
-            })
-        }
-        if (amax) block_amax_commit(am, amax);
-        if (!stats) return;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                cs[h][j] += __shfl_xor(cs[h][j], 32, 64);
-                cq[h][j] += __shfl_xor(cq[h][j], 32, 64);
-            }
-        if (lane < 32) {
-            float* st = stats + (long long)(mw / GBM) * 2 * stats_ld;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int n = nw + 32 * j + lane;
-                if (n < N) { st[n] = cs[0][j] + cs[1][j]; st[stats_ld + n] = cq[0][j] + cq[1][j]; }
-            }
-        }
-        if (!ymm) return;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            cmx[j] = fmaxf(cmx[j], __shfl_xor(cmx[j], 32, 64));
-            cmn[j] = fminf(cmn[j], __shfl_xor(cmn[j], 32, 64));
-        }
-        __syncthreads();  // scratch aliases the operand LDS
-        if (lane < 32) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = wn * 64 + 32 * j + lane;
-                scratch[wm * GBN + c] = cmx[j];
-                scratch[(NWM + wm) * GBN + c] = cmn[j];
-            }
-        }
-        __syncthreads();
-        if (tid < GBN) {
-            const int n = (nw - wn * 64) + tid;
-            if (n < N) {
-                float mx = scratch[tid], mn = scratch[NWM * GBN + tid];
-#pragma unroll
-                for (int w = 1; w < NWM; ++w) {
-                    mx = fmaxf(mx, scratch[w * GBN + tid]);
-                    mn = fminf(mn, scratch[(NWM + w) * GBN + tid]);
-                }
-                atomicMax(ymm + n, fkey(mx));
-                atomicMin(ymm + ymm_ld + n, fkey(mn));
-            }
-        }
-    }
 };
 using EpiStore = EpiStoreW<2>;
 template <class EP> struct IsEpiStoreW : std::false_type {};
 template <int WM, class OT, bool ACC, bool FUSE> struct IsEpiStoreW<EpiStoreW<WM, OT, ACC, FUSE>> : std::true_type {};
-
-// EpiConvT2x2 for the transposed accumulators of gemm_deep_kernel<..., TRO = true>: acc[i][j][r] = C[m][n] at m = mw + 32 i +
-// (lane & 31), n = nw + 32 j + (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Four consecutive n (r = 4q..4q+3) are four consecutive
-// output channels of one sub-pixel ij (Co % 8 == 0: an 8-aligned column group never straddles two sub-pixels, so ij is
-// wave-uniform), stored as one float4; needs y, ldy 16-byte aligned and M % 128 == N % 128 == 0 (host checks).
-struct EpiConvT2x2T {
-    float* y; long long ldy; const float* bias; int H, W, Co, M, N;
-    float* amax = nullptr;
-    __device__ __forceinline__ void operator()(f32x16 (&acc)[2][2], int mw, int nw, int lane, int, int, float*,
-                                               int) const {
-        float am = 0.f;
-        const int hw = H * W, nu = __builtin_amdgcn_readfirstlane(nw), lh = 4 * (lane >> 5);
-        float* px[2];   // the lane's input pixel m -> its output 2x2 block's first pixel
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = mw + 32 * i + (lane & 31), b = m / hw, rem = m - b * hw, h = rem / W, w = rem - h * W;
-            px[i] = y + ((long long)(b * 2 * H + 2 * h) * (2 * W) + 2 * w) * ldy + lh;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int nb = nu + 32 * j + 8 * q, ij = nb / Co, co = nb - ij * Co;   // wave-uniform
-                const long long off = ((long long)(ij >> 1) * (2 * W) + (ij & 1)) * ldy + co;
-                const float* bp = bias + co + lh;   // (the packed parameter buffer: not 16-byte aligned in general)
-                const float4 bv = bias ? make_float4(bp[0], bp[1], bp[2], bp[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 v = make_float4(acc[i][j][4 * q] + bv.x, acc[i][j][4 * q + 1] + bv.y,
-                                                 acc[i][j][4 * q + 2] + bv.z, acc[i][j][4 * q + 3] + bv.w);
-                    *reinterpret_cast<float4*>(px[i] + off) = v;
-                    am = fmaxf(am, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-                }
-            }
-        if (amax) block_amax_commit(am, amax);
-    }
-};
 
 struct EpiConvT2x2 {  // row m = (n,h,w) input pixel, col = ij*Co + co  ->  y[n, 2h+i, 2w+j, co] = acc + b[co]
     float* y; long long ldy; const float* bias; int H, W, Co, M, N;
@@ -1190,10 +1036,7 @@ struct DeepConvT2x2GatherA { // the ConvT 2x2 input gradient (LdConvT2x2GatherA)
         return ((long long)(ij >> 1) * (2 * W) + (ij & 1)) * lddy + co;
     }
 };
-// TRO (round 6): the MFMAs take B as their first operand, so each accumulator holds the tile transposed — a lane keeps one
-// row m (pixel) and, for r = 4q..4q+3, four consecutive columns n: the epilogue (EpiConvT2x2T) stores 16 bytes per
-// instruction instead of 4 (the scatter epilogue issued 64 dword stores per lane per tile, which nothing overlapped)
-template <int NT, class AL, class EP, int MINB, bool TRO = false>
+template <int NT, class AL, class EP, int MINB>
 __global__ __launch_bounds__(GTHREADS, MINB) void gemm_deep_kernel(AL al, const __bf16* __restrict__ bp, int N,
                                                                   const float* amax_a, const float* amax_b, EP ep,
                                                                   int K) {
@@ -1265,10 +1108,7 @@ __global__ __launch_bounds__(GTHREADS, MINB) void gemm_deep_kernel(AL al, const 
                 fa[i][t] = *reinterpret_cast<const bf16x8*>(ab + t * XPLANE + aoff[i]);
                 fb[i][t] = *reinterpret_cast<const bf16x8*>(bb + t * XPLANE + boff[i]);
             }
-        auto mf = [&](const bf16x8& x, const bf16x8& w, const f32x16& c) {   // x: the A fragment (rows m)
-            if constexpr (TRO) return xmfma<NT>(w, x, c);
-            else return xmfma<NT>(x, w, c);
-        };
+        auto mf = [&](const bf16x8& x, const bf16x8& w, const f32x16& c) { return xmfma<NT>(x, w, c); };
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1306,19 +1146,6 @@ __global__ __launch_bounds__(GTHREADS, MINB) void gemm_deep_kernel(AL al, const 
     ep(acc, m0 + wm * 64, n0 + wn * 64, lane, wm, wn, reinterpret_cast<float*>(smem), tid);
 }
 
-// $CDM_GEMM_MINB: 4 or 2 resident blocks per CU asked of the compiler; default 4 for h3 (profiles/r3_ab_gemm_minb.txt),
-// 2 for the one-term bf16 arithmetic, whose 4-block form spills 51 VGPRs (with the bf16 knobs below, same-box A/B:
-// C4 27.95-28.02 -> 27.73-27.75 ms per step, profiles/r4_ab_c4_knobs.txt)
-static int gemm_minb(int nterm) {
-    static const int v = [] { const char* e = getenv("CDM_GEMM_MINB"); return e ? atoi(e) : 0; }();
-    return v > 0 ? v : (nterm == 1 ? 2 : 4);
-}
-
-static int gemm_order() {   // $CDM_GEMM_ORDER: 1 operand-sharing block order (default), 0 grid order
-    static const int v = [] { const char* e = getenv("CDM_GEMM_ORDER"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
 // SA<NS>/SB<NS> are stager templates; splits as launch_gemm (K-tile ranges over blockIdx.z)
 template <template <int> class SAT, template <int> class SBT, class EP, bool XCD_REMAP, class MkA, class MkB>
 static int launch_gemm_x3(MkA mka, MkB mkb, const EP& ep, int M, int N, int K, int splits, int nterm,
@@ -1329,27 +1156,18 @@ static int launch_gemm_x3(MkA mka, MkB mkb, const EP& ep, int M, int N, int K, i
     const int per = (ktiles + splits - 1) / splits;
     splits = ktiles > 0 ? (ktiles + per - 1) / per : 1;
     dim3 grid((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits);
-    const int order = gemm_order();
+    const int order = 1;   // the operand-sharing block order (0: grid order)
+    // resident blocks per CU asked of the compiler: 4 for h3 (profiles/r3_ab_gemm_minb.txt), the default 2 for the
+    // one-term bf16 arithmetic, whose 4-block form spills 51 VGPRs (profiles/r4_ab_c4_knobs.txt)
     switch (nterm) {
-        case 1:
-            if (gemm_minb(1) == 4)
-                hipLaunchKernelGGL((gemm_x3_kernel<SAT<1>, SBT<1>, EP, 1, XCD_REMAP, 1, 4>), grid, dim3(GTHREADS), 0, s,
-                                   mka.template make<1>(), mkb.template make<1>(), ep, K, per, order);
-            else
-                hipLaunchKernelGGL((gemm_x3_kernel<SAT<1>, SBT<1>, EP, 1, XCD_REMAP>), grid, dim3(GTHREADS), 0, s,
-                                   mka.template make<1>(), mkb.template make<1>(), ep, K, per, order);
-            break;
+        case 1: hipLaunchKernelGGL((gemm_x3_kernel<SAT<1>, SBT<1>, EP, 1, XCD_REMAP>), grid, dim3(GTHREADS), 0, s,
+                                   mka.template make<1>(), mkb.template make<1>(), ep, K, per, order); break;
         case 3: hipLaunchKernelGGL((gemm_x3_kernel<SAT<3>, SBT<3>, EP, 3, XCD_REMAP>), grid, dim3(GTHREADS), 0, s,
                                    mka.template make<3>(), mkb.template make<3>(), ep, K, per, order); break;
         case NT_H3:
-            if (gemm_minb(NT_H3) == 4)
-                hipLaunchKernelGGL((gemm_x3_kernel<SAT<NT_H3>, SBT<NT_H3>, EP, NT_H3, XCD_REMAP, 1, 4>), grid,
-                                   dim3(GTHREADS), 0, s, mka.template make<NT_H3>(), mkb.template make<NT_H3>(), ep, K,
-                                   per, order);
-            else
-                hipLaunchKernelGGL((gemm_x3_kernel<SAT<NT_H3>, SBT<NT_H3>, EP, NT_H3, XCD_REMAP>), grid,
-                                   dim3(GTHREADS), 0, s, mka.template make<NT_H3>(), mkb.template make<NT_H3>(), ep, K,
-                                   per, order);
+            hipLaunchKernelGGL((gemm_x3_kernel<SAT<NT_H3>, SBT<NT_H3>, EP, NT_H3, XCD_REMAP, 1, 4>), grid,
+                               dim3(GTHREADS), 0, s, mka.template make<NT_H3>(), mkb.template make<NT_H3>(), ep, K,
+                               per, order);
             break;
         case 6: hipLaunchKernelGGL((gemm_x3_kernel<SAT<6>, SBT<6>, EP, 6, XCD_REMAP>), grid, dim3(GTHREADS), 0, s,
                                    mka.template make<6>(), mkb.template make<6>(), ep, K, per, order); break;
@@ -1426,19 +1244,20 @@ struct PreBnReluSums {
 constexpr int HBM_ = 256;          // output pixels per block
 constexpr int HTHREADS = 512;
 
-// ABL: timing-ablation bits for tools/conv_ablation.py (1 = shipped for NS <= 2; x6 keeps 0: its registers do not fit
-// the second fragment set): 1 fragment prefetch (the next
-// tap's fragments are read during the current tap's MFMAs: 0.94 -> 0.84 ms), 2 every MFMA issued twice, 4 B
-// staged once (stale afterwards), 8 halo stored without the term split, 16 no barriers in the main loop,
-// 32 halo loaded for the first chunk only, 64 / 128 prefetch schedules: 2 reads per MFMA gap / all reads after the
-// tap's first MFMA, 256 staggered halo split (waves 0-3 split + store the next chunk's halo after their last kernel
-// row's MFMAs, waves 4-7 before them, so each SIMD pairs one wave's VALU with its partner's MFMAs), 512 static
-// priority 1 for waves 4-7, 16384 epilogue skipped (behind a never-taken branch: the MFMAs stay live; round 6: 0.753 ->
-// 0.672 ms at 16 tiles per block — the epilogue's 537 MB of y, stored by every block at the same time, drains at ~6.6
-// TB/s with no MFMA running; issuing the next chunk's loads ahead of those stores measured slower, 0.822 -> 0.833 ms)
-// XT: element type of the source x (and of PRE's y): bf16 for C4's fused-chain activations / gradients
-template <int NT, int WT, class EP, bool XCD_REMAP, int ABL = (NT >= 6 ? 0 : 1), class PRE = PreNone, class XT = float>
-__global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* __restrict__ x, int H, int Cin,
+// Compile-time parameters besides the arithmetic NT and the row width WT:
+//   ONEB (one bf16 term only): B of all 9 taps of a chunk in one buffer and one barrier per chunk.
+//   DEEP (with ONEB, forward staging only): the halo is loaded two chunks ahead.
+//   The fragment prefetch (the next tap's fragments are read during the current tap's MFMAs: 0.94 -> 0.84 ms) is on
+//   for NS <= 2 and off for x6, whose registers do not fit the second fragment set.
+//   XT: element type of the source x (and of PRE's y): bf16 for C4's fused-chain activations / gradients.
+// Dispatched: x6 <6>, x3 / h3 / wide rows <NT>, one-term bf16 <1, ONEB>, one-term forward with Cin % 32 == 0
+// <1, ONEB, DEEP>.  The kernel carried a 15-bit ablation mask until commit b6284cd (timing ablations, the 2-reads-per-
+// gap / reads-after-first-MFMA prefetch schedules, static wave priority, the halo split interleaved into the MFMAs'
+// scheduling region, 128 x 64 "tall" wave tiles, the one-term three-barrier schedule): all measured neutral or slower;
+// the figures are in DESIGN.md sections 3 and 8 and profiles/r6_conv_ablation.jsonl, the code in that commit.
+template <int NT, int WT, class EP, bool XCD_REMAP, bool ONEB = false, bool DEEP = false, class PRE = PreNone,
+          class XT = float>
+__global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* __restrict__ x, int H, int Cin,
                                                                       int ldx, const __bf16* __restrict__ wx3,
                                                                       int Cout, const float* amax_x,
                                                                       const float* amax_w, EP ep, PRE pre,
@@ -1447,45 +1266,33 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     // every other block in 10 ns
     // ticks (halo_delay: desynchronises the blocks' epilogue store bursts)
     const int stg = stgd & 1;
-    constexpr bool bearly = true;   // B of the next chunk's first kernel row fetched in row 1 (round 6, profiles/r6_ab_halo_bearly.txt)
     constexpr int NS = XTerms<NT>::NS;
-    // TALL (ABL 8192, one bf16 term only): 4 waves (one per SIMD, 512 registers each: the accumulators live in AGPRs) as
-    // 2 (M) x 2 (N) of 128 x 64 — 4 row blocks of 32 pixels per wave.  The one-term MFMA reads 1 KiB of fragments per
-    // 32x32x16 product from LDS at 64 x 64 (the CU's LDS rate at full MFMA rate); 128 x 64 reads 0.75 KiB.  Same
-    // 256-pixel x 128-channel block tile and LDS images as the 8-wave form; launched with 256 threads.  Measured (round
-    // 4, profiles/r4_ab_halo_tall.txt): bit-identical C4 train steps, but 29.3 vs 27.5 ms — one wave per SIMD leaves
-    // the staging and barrier waits uncovered (forward 64^2 414 vs 326 us).  Kept as an ablation bit, not dispatched.
-    constexpr bool TALL = (ABL & 8192) != 0;
-    static_assert(!TALL || NS == 1, "tall wave tiles: the one-term images only");
-    constexpr int MI = TALL ? 4 : 2;                  // 32-row blocks per wave
-    constexpr int NTH = TALL ? 256 : HTHREADS;        // threads per block
+    constexpr bool PREFETCH = NS <= 2;                // register double buffer of the A / B fragments
     constexpr int HB = HBM_;                          // output pixels per tile
     constexpr int ROWS = HB / WT, HR = ROWS + 2, HC = WT + 2, HPX = HR * HC;
-    constexpr int HQ = (HPX * 4 + NTH - 1) / NTH;   // float4 halo pieces per thread
+    constexpr int HQ = (HPX * 4 + HTHREADS - 1) / HTHREADS;   // float4 halo pieces per thread
     // halo planes padded to HQ x 512 pieces where LDS allows: every piece then has a slot (past-the-halo pieces
     // write unused padding), so the split + store has no branches and can share a scheduling region with MFMAs
-    constexpr int HPXA = HQ * NTH / 4;
-    // ONEB (ABL 2048, one bf16 term only): B of all 9 taps of a chunk in one buffer, one barrier per chunk (36 MFMAs per
+    constexpr int HPXA = HQ * HTHREADS / 4;
+    // ONEB (one bf16 term only): B of all 9 taps of a chunk in one buffer, one barrier per chunk (36 MFMAs per
     // wave between barriers instead of 12; the one-term chunk is too short to pay three barrier drains)
-    constexpr bool ONEB = (ABL & 2048) != 0;
     static_assert(!ONEB || NS == 1, "one barrier per chunk: the one-term images only");
     constexpr int BGR = ONEB ? 3 : 1;                 // B groups (kernel rows) per buffer
-    // DEEP (ABL 4096, with ONEB, forward staging only): the halo of chunk q+2 is loaded while chunk q computes and
+    // DEEP (with ONEB, forward staging only): the halo of chunk q+2 is loaded while chunk q computes and
     // chunk q+1 (loaded one chunk earlier) is stored, so a halo load has two chunks to arrive instead of one (the
     // one-term chunk is short against HBM latency); two halo register sets, Cin % 32 == 0
-    constexpr bool DEEP = (ABL & 4096) != 0;
     static_assert(!DEEP || (ONEB && !PRE::on), "two-deep halo prefetch: one-term forward staging only");
     constexpr bool HPAD = (2 * NS * HPXA * XBK + 2 * 3 * BGR * NS * XPLANE) * 2 + 7 * 256 * 4 <= 160 * 1024;
     constexpr int HPLANE = (HPAD ? HPXA : HPX) * XBK;   // bf16 per halo term plane
     constexpr int BPL = 3 * NS;                       // B planes per group (3 taps x NS terms)
-    constexpr int BQ = (BGR * BPL * 256 + NTH - 1) / NTH;  // 16-byte B pieces per thread
+    constexpr int BQ = (BGR * BPL * 256 + HTHREADS - 1) / HTHREADS;  // 16-byte B pieces per thread
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * NS * HPLANE + 2 * BGR * BPL * XPLANE];
     __bf16* Hs = smem;                                // [buf][term][halo pixel][16 ch] (xoff swizzle)
     __bf16* Bs = smem + 2 * NS * HPLANE;              // [buf][tap dx][term][col][16 k] (xoff swizzle)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    if ((ABL & 512) || (stgd & 2)) {   // static priority for the second-dispatched half (stgd bit 1: $CDM_HALO_PRIO)
+    if (stgd & 2) {   // static priority for the second-dispatched half (stgd bit 1: $CDM_HALO_PRIO)
         if (wave >= 4) __builtin_amdgcn_s_setprio(1);
     }
     // the block's tpb 256-pixel tiles, run one after the other: the next tile's first halo and B are fetched
@@ -1517,14 +1324,14 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     constexpr int NCOEF = PRE::kind == 1 ? 7 : (PRE::kind == 2 ? 2 : 0);
     __shared__ __attribute__((aligned(16))) float bcs[NCOEF ? NCOEF * 256 : 4];
     if constexpr (NCOEF > 0) {
-        for (int i = tid; i < NCOEF * Cin; i += NTH) {
+        for (int i = tid; i < NCOEF * Cin; i += HTHREADS) {
             const int k = i / Cin;
             bcs[i] = pre.p[k][i - k * Cin];
         }
         __syncthreads();
     }
 
-    f32x16 acc[MI][2];
+    f32x16 acc[2][2];
 
     // ---- halo staging: piece q = (halo pixel q>>2, channels 4(q&3)..+3); addresses fixed per block ----
     // Every global load of the main loop is issued unconditionally (pieces outside the image load a valid dummy
@@ -1546,7 +1353,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         const int m0 = t * HB, img = m0 / hw, h0 = (m0 - img * hw) / WT;
 #pragma unroll
         for (int j = 0; j < HQ; ++j) {
-            const int q = tid + j * NTH;
+            const int q = tid + j * HTHREADS;
             const int hp = q >> 2, c4 = q & 3;
             const int hr = hp / HC, hc = hp - hr * HC;
             const int ih = h0 - 1 + hr, iw = hc - 1;
@@ -1559,7 +1366,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     };
 #pragma unroll
     for (int j = 0; j < HQ; ++j) {
-        const int q = tid + j * NTH;
+        const int q = tid + j * HTHREADS;
         hdst[j] = (HPAD || q < HPX * 4) ? xoff(q >> 2, (q & 3) * 4) : -1;
     }
     setup_tile(t_first);
@@ -1574,9 +1381,6 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         }
     };
     auto gload_halo = [&](int cc) {
-        if constexpr (ABL & 32) {
-            if (cc > 0) return;
-        }
         const char* xb = reinterpret_cast<const char*>(x + cc * 16);
 #pragma unroll
         for (int j = 0; j < HQ; ++j) hreg[j] = Act<XT>::load4(xb + hxo[j]);
@@ -1611,7 +1415,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
                     if (pre.dyo != nullptr && blockIdx.y == 0) {   // block-uniform
                         // piece j's halo pixel (hr, hc) is one of the tile's own output pixels: rows 1..ROWS, columns
                         // 1..WT of the halo (always inside the image); hxo[j] addresses it in g, same layout as dyo
-                        const int q = tid + j * NTH, hp = q >> 2, hr = hp / HC, hc = hp - hr * HC;
+                        const int q = tid + j * HTHREADS, hp = q >> 2, hr = hp / HC, hc = hp - hr * HC;
                         if (q < HPX * 4 && hr >= 1 && hr <= ROWS && hc >= 1 && hc <= WT) {
                             char* o = reinterpret_cast<char*>(pre.dyo) + hxo[j] + (size_t)cc * 16 * XSZ;
                             if constexpr (std::is_same<XT, float>::value)
@@ -1628,12 +1432,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xv[e] = inb(j) ? xv[e] : 0.f;   // zero padding (transform not applied)
                 u32x2 tm[3];
-                if constexpr (ABL & 8) {
-                    const u32x2 raw{__float_as_uint(xv[0]), __float_as_uint(xv[1])};
-                    tm[0] = raw; tm[1] = u32x2{__float_as_uint(xv[2]), __float_as_uint(xv[3])}; tm[2] = raw;
-                } else {
-                    split_pk4<NT>(xv, sx, tm);
-                }
+                split_pk4<NT>(xv, sx, tm);
                 __bf16* d = base + hdst[j];
 #pragma unroll
                 for (int k = 0; k < NS; ++k) *reinterpret_cast<u32x2*>(d + k * HPLANE) = tm[k];
@@ -1657,7 +1456,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     unsigned bpo[BQ];
 #pragma unroll
     for (int j = 0; j < BQ; ++j) {
-        const int q = tid + j * NTH;
+        const int q = tid + j * HTHREADS;
         // ONEB: plane pl = kernel row * BPL + tap (NS == 1); group gr of the chunk at the global group stride
         const int plg = min(q >> 8, BGR * BPL - 1), gr = plg / BPL, pl = plg - gr * BPL;
         const int dx = pl / NS, t = pl - dx * NS, half = q & 1;
@@ -1669,11 +1468,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
 #pragma unroll
         for (int j = 0; j < BQ; ++j) breg[j] = *reinterpret_cast<const u32x4*>(gb + bpo[j]);
     };
-    int bstores = 0;
     auto store_b = [&](int boff, const u32x4 (&breg)[BQ]) {   // into Bs + boff
-        if constexpr (ABL & 4) {
-            if (bstores++ >= 2) return;
-        }
         // an opaque offset: the compiler can no longer prove the stores disjoint from the current kernel row's
         // fragment reads, so it keeps them after those reads instead of pulling them (and their load waits) up
         // among the first MFMAs
@@ -1681,7 +1476,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         __bf16* base = Bs + boff;
 #pragma unroll
         for (int j = 0; j < BQ; ++j) {
-            const int q = tid + j * NTH;
+            const int q = tid + j * HTHREADS;
             if (q < BGR * BPL * 256)
                 *reinterpret_cast<u32x4*>(base + (q >> 8) * XPLANE + xoff((q & 255) >> 1, (q & 1) * 8)) = breg[j];
         }
@@ -1689,62 +1484,38 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
 
     // per-lane halo pixel of each A fragment row (tap (0,0) origin)
     const int kh = (lane >> 5) * 8;
-    int hp0[MI];
+    int hp0[2];
 #pragma unroll
-    for (int i = 0; i < MI; ++i) {
-        const int p = wm * (32 * MI) + 32 * i + (lane & 31);
+    for (int i = 0; i < 2; ++i) {
+        const int p = wm * 64 + 32 * i + (lane & 31);
         const int r = p / WT, c = p - r * WT;
         hp0[i] = r * HC + c;
     }
     int boff[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) boff[j] = xoff(wn * 64 + 32 * j + (lane & 31), kh);
-    // A fragment offset of tap (dy, dx), row block i (fixed per lane); TALL computes them per kernel row instead
-    // (36 registers held across the loop would not fit beside the 128 accumulators)
-    int aoff[3][3][TALL ? 1 : 2];
-    if constexpr (!TALL) {
+    // A fragment offset of tap (dy, dx), row block i (fixed per lane)
+    int aoff[3][3][2];
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
+    for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
+        for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) aoff[dy][dx][i] = xoff(hp0[i] + dy * HC + dx, kh);
-    }
-    auto afrag = [&](int dy, int dx, int i) {
-        if constexpr (TALL) return xoff(hp0[i] + dy * HC + dx, kh);
-        else return aoff[dy][dx][i];
-    };
+            for (int i = 0; i < 2; ++i) aoff[dy][dx][i] = xoff(hp0[i] + dy * HC + dx, kh);
 
-    auto hmfma = [&](const bf16x8& fa_, const bf16x8& fb_, const f32x16& c_) {
-        if constexpr (ABL & 2) return xmfma<NT>(fa_, fb_, xmfma<NT>(fa_, fb_, c_));
-        else return xmfma<NT>(fa_, fb_, c_);
-    };
     // the 3 taps (dx) of kernel row dy of the current chunk: fragments from the halo image a and B group b
-    // vtag = std::integral_constant<int, V>: V > 0 interleaves V VALU instructions (and a DS write every 4th MFMA)
-    // into every MFMA gap — the halo split of the next chunk, placed in the same scheduling region (ABL 1024)
-    auto compute = [&](int dy, const __bf16* a, const __bf16* b, auto vtag) {
-        constexpr int V = decltype(vtag)::value;
-        int nmf = 0;
-        auto mf1 = [&]() {   // one MFMA slot of the pinned schedule
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if constexpr (V > 0) {
-                __builtin_amdgcn_sched_group_barrier(0x002, V, 0);
-                // the LDS writes after the last fragment read (they may alias it): in the last tap
-                if (++nmf > 24 && (nmf & 1) == 0) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-            }
-        };
+    auto compute = [&](int dy, const __bf16* a, const __bf16* b) {
         // register double buffer: the fragments of tap dx+1 are read while the MFMAs of tap dx issue
-        bf16x8 FA[2][MI][NS], FB[2][2][NS];
+        bf16x8 FA[2][2][NS], FB[2][2][NS];
         auto ldfrag = [&](int buf, int dx) {
 #pragma unroll
             for (int t = 0; t < NS; ++t)
 #pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    FA[buf][i][t] = *reinterpret_cast<const bf16x8*>(a + t * HPLANE + afrag(dy, dx, i));
-                    if (i < 2) FB[buf][i][t] = *reinterpret_cast<const bf16x8*>(b + (dx * NS + t) * XPLANE + boff[i]);
+                for (int i = 0; i < 2; ++i) {
+                    FA[buf][i][t] = *reinterpret_cast<const bf16x8*>(a + t * HPLANE + aoff[dy][dx][i]);
+                    FB[buf][i][t] = *reinterpret_cast<const bf16x8*>(b + (dx * NS + t) * XPLANE + boff[i]);
                 }
         };
-        constexpr bool PREFETCH = ABL & 1;
         if constexpr (PREFETCH) ldfrag(0, 0);
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
@@ -1757,16 +1528,16 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
             const auto& fb = FB[dx & 1];
             // term-major: the hh products issue first, the cross terms after
 #pragma unroll
-            for (int i = 0; i < MI; ++i)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = hmfma(fa[i][0], fb[j][0], acc[i][j]);
+                for (int j = 0; j < 2; ++j) acc[i][j] = xmfma<NT>(fa[i][0], fb[j][0], acc[i][j]);
             if constexpr (NT >= 3) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        acc[i][j] = hmfma(fa[i][0], fb[j][1], acc[i][j]);
-                        acc[i][j] = hmfma(fa[i][1], fb[j][0], acc[i][j]);
+                        acc[i][j] = xmfma<NT>(fa[i][0], fb[j][1], acc[i][j]);
+                        acc[i][j] = xmfma<NT>(fa[i][1], fb[j][0], acc[i][j]);
                     }
             }
             if constexpr (NT >= 6) {
@@ -1774,58 +1545,29 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        acc[i][j] = hmfma(fa[i][1], fb[j][1], acc[i][j]);
-                        acc[i][j] = hmfma(fa[i][0], fb[j][2], acc[i][j]);
-                        acc[i][j] = hmfma(fa[i][2], fb[j][0], acc[i][j]);
+                        acc[i][j] = xmfma<NT>(fa[i][1], fb[j][1], acc[i][j]);
+                        acc[i][j] = xmfma<NT>(fa[i][0], fb[j][2], acc[i][j]);
+                        acc[i][j] = xmfma<NT>(fa[i][2], fb[j][0], acc[i][j]);
                     }
             }
         }
         if constexpr (PREFETCH) {
             // pin the interleave: the next tap's fragment reads go one per MFMA gap of the current tap
-            constexpr int MF = 2 * MI * (NT >= 6 ? 6 : (NT >= 3 ? 3 : 1)), RD = (MI + 2) * NS;
-            if constexpr (V > 0) __builtin_amdgcn_sched_group_barrier(0x020, BQ, 0);   // next B loads first
+            constexpr int MF = 4 * (NT >= 6 ? 6 : (NT >= 3 ? 3 : 1)), RD = 4 * NS;
             __builtin_amdgcn_sched_group_barrier(0x100, RD, 0);          // tap 0 fragments
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
-                if constexpr (ABL & 64) {          // two reads per gap: the next tap's fragments land early
 #pragma unroll
-                    for (int k = 0; k < RD / 2; ++k) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, MF - RD / 2, 0);
-                } else if constexpr (ABL & 128) {  // all reads after the tap's first MFMA
+                for (int k = 0; k < RD; ++k) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, RD, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, MF - 1, 0);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < RD; ++k) {
-                        mf1();
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    if constexpr (V > 0) {
-#pragma unroll
-                        for (int k = 0; k < MF - RD; ++k) mf1();
-                    } else {
-                        __builtin_amdgcn_sched_group_barrier(0x008, MF - RD, 0);
-                    }
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
+                __builtin_amdgcn_sched_group_barrier(0x008, MF - RD, 0);
             }
-            if constexpr (V > 0) {                                        // last tap
-#pragma unroll
-                for (int k = 0; k < MF; ++k) mf1();
-            } else {
-                __builtin_amdgcn_sched_group_barrier(0x008, MF, 0);
-            }
+            __builtin_amdgcn_sched_group_barrier(0x008, MF, 0);          // last tap
         }
     };
-    using V0 = std::integral_constant<int, 0>;
-    using VH = std::integral_constant<int, (ABL & 1024) ? 4 : 0>;
 
-    auto sync = [&]() {
-        if constexpr (!(ABL & 16)) __syncthreads();
-    };
     gload_halo(0);
     gload_b(0, bregA);
     store_halo(Hs, 0);
@@ -1840,7 +1582,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     for (int kt = 0, t = t_first; kt < tpb && t < mtiles; ++kt, t += t_step) {
     const bool nextt = kt + 1 < tpb && t + t_step < mtiles;
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -1857,14 +1599,14 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         if (cc + 2 == nchunks && nextt) setup_tile(t + t_step);
         // chunk q+2: this tile's cc + 2, or the next tile's cc + 2 - nchunks (a dummy reload past the block's end)
         gload_halo_to(hl, ml, cc + 2 < nchunks ? cc + 2 : cc + 2 - nchunks);
-        compute(0, a, bcur, V0{});
-        compute(1, a, bcur + BPL * XPLANE, V0{});
-        compute(2, a, bcur + 2 * BPL * XPLANE, V0{});
+        compute(0, a, bcur);
+        compute(1, a, bcur + BPL * XPLANE);
+        compute(2, a, bcur + 2 * BPL * XPLANE);
         if (has1) {
             store_halo_set(hs, ms, Hs + (hb ^ 1) * NS * HPLANE, morec ? cc + 1 : 0);
             store_b((bb ^ 1) * 3 * BPL * XPLANE, bregA);
         }
-        sync();
+        __syncthreads();
         bb ^= 1;
         hb ^= 1;
     };
@@ -1881,15 +1623,15 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         gload_b(morec ? (cc + 1) * 3 : 0, bregA);
         if (!morec && nextt) setup_tile(t + t_step);
         gload_halo(morec ? cc + 1 : 0);
-        compute(0, a, bcur, V0{});
-        compute(1, a, bcur + BPL * XPLANE, V0{});
+        compute(0, a, bcur);
+        compute(1, a, bcur + BPL * XPLANE);
         // staggered (stg): waves 4-7 split + store the next chunk before the last kernel row's MFMAs, waves 0-3 after
         // them (both buffers idle since the previous chunk's barrier)
-        const bool early = stg && __builtin_amdgcn_readfirstlane(wave) >= NTH / 128;   // wave-uniform (scalar branch)
+        const bool early = stg && __builtin_amdgcn_readfirstlane(wave) >= 4;   // wave-uniform (scalar branch)
         if (morec && early) { store_halo(Hs + (hb ^ 1) * NS * HPLANE, cc + 1); store_b((bb ^ 1) * 3 * BPL * XPLANE, bregA); }
-        compute(2, a, bcur + 2 * BPL * XPLANE, V0{});
+        compute(2, a, bcur + 2 * BPL * XPLANE);
         if (morec && !early) { store_halo(Hs + (hb ^ 1) * NS * HPLANE, cc + 1); store_b((bb ^ 1) * 3 * BPL * XPLANE, bregA); }
-        sync();
+        __syncthreads();
         bb ^= 1;
         hb ^= 1;
     }
@@ -1903,46 +1645,37 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
         gload_b(g0 + 2, bregB);
         if (!morec && nextt) setup_tile(t + t_step);
         gload_halo(morec ? cc + 1 : 0);   // (a dummy reload of chunk 0 after the block's last chunk)
-        compute(0, a, Bs + bb * BPL * XPLANE, V0{});
+        compute(0, a, Bs + bb * BPL * XPLANE);
         store_b((bb ^ 1) * BPL * XPLANE, bregA);
-        sync();
+        __syncthreads();
         bb ^= 1;
-        // dy = 1 (bearly: B of the next chunk's dy = 0 fetched here, into the register set stored in dy = 0, so it has a
-        // whole group's MFMAs to arrive instead of being stored right after the MFMAs it was issued before)
-        if constexpr (bearly) gload_b(morec ? g0 + 3 : 0, bregA);
-        compute(1, a, Bs + bb * BPL * XPLANE, V0{});
+        // dy = 1: B of the next chunk's dy = 0 is fetched here, into the register set stored in dy = 0, so it has a
+        // whole group's MFMAs to arrive (round 6, profiles/r6_ab_halo_bearly.txt, r6_ab_halo_bearly_const.txt)
+        gload_b(morec ? g0 + 3 : 0, bregA);
+        compute(1, a, Bs + bb * BPL * XPLANE);
         store_b((bb ^ 1) * BPL * XPLANE, bregB);
-        sync();
+        __syncthreads();
         bb ^= 1;
-        // dy = 2: fetch B of the next chunk's dy = 0; split + store the next halo (buffer idle since chunk cc-1)
-        // ahead of this group's MFMAs, so its VALU work interleaves with them; B after them (just issued)
-        if constexpr (!bearly) gload_b(morec ? g0 + 3 : 0, bregA);
-        // staggered split (ABL 256, or stg at run time: $CDM_HALO_STAGGER): waves 0-3 split + store the next halo
-        // after this kernel row's MFMAs, waves 4-7 before them, so each SIMD pairs one wave's VALU with its partner's
-        // MFMAs (wave-uniform)
-        const bool late = ((ABL & 256) || stg) && wave < NTH / 128;
+        // dy = 2: split + store the next halo (buffer idle since chunk cc-1) ahead of this group's MFMAs, so its VALU
+        // work interleaves with them; B after them.  Staggered split (stg: halo_stagger): waves 0-3 split + store the
+        // next halo after this kernel row's MFMAs, waves 4-7 before them, so each SIMD pairs one wave's VALU with its
+        // partner's MFMAs (wave-uniform)
+        const bool late = stg && wave < 4;
         // (round 6) after the block's last chunk these stores write the next tile's chunk 0 (halo and B, fetched during
         // this chunk; setup_tile moved the halo offsets) into the buffers its first chunk reads — the work the post-loop
         // stores did — so the stores need no `more chunks` condition (each condition was one more basic block splitting
         // the MFMAs' scheduling region; after the last tile they rewrite idle buffers)
         const int cn = morec ? cc + 1 : 0;
-        if constexpr (!(ABL & 1024)) {
-            if (!late) store_halo(Hs + (hb ^ 1) * NS * HPLANE, cn);
-        }
-        compute(2, a, Bs + bb * BPL * XPLANE, VH{});
-        if constexpr (ABL & 1024) {
-            // after the MFMAs in program order (its LDS writes may alias the fragment reads) but in their scheduling
-            // region: the split's VALU fills the MFMA gaps
-            store_halo(Hs + (hb ^ 1) * NS * HPLANE, cn);
-        }
+        if (!late) store_halo(Hs + (hb ^ 1) * NS * HPLANE, cn);
+        compute(2, a, Bs + bb * BPL * XPLANE);
         if (late) store_halo(Hs + (hb ^ 1) * NS * HPLANE, cn);
         store_b((bb ^ 1) * BPL * XPLANE, bregA);
-        sync();
+        __syncthreads();
         bb ^= 1;
         hb ^= 1;
     }
     }
-    if constexpr (!TALL) unscale<NT>(acc, sx, op_scale<NT>(amax_w));   // (one term: unscaled)
+    unscale<NT>(acc, sx, op_scale<NT>(amax_w));   // (one term: unscaled)
     if constexpr (ONEB && !DEEP) {   // (the three-barrier schedule stored them in its last kernel row)
         if (nextt) {   // the next tile's chunk 0 (its loads were issued during the last chunk) into the halo / B buffers
             // idle since the last chunk's closing barrier, ahead of the epilogue: its prefetch registers die before the
@@ -1953,15 +1686,7 @@ __global__ __launch_bounds__((ABL & 8192) ? 256 : HTHREADS, 1) void conv3x3_halo
     }
     // epilogue scratch (stats / max-min: 4 KiB): the other halo buffer (>= 24 KiB), last read by the final chunk
     // before its closing barrier
-    if constexpr (TALL)
-        ep.tall(acc, t * HB + wm * 128, n0 + wn * 64, lane, wm, wn, reinterpret_cast<float*>(Hs + (hb ^ 1) * NS * HPLANE),
-                tid);
-    else if constexpr (ABL & 16384) {   // timing ablation: the epilogue skipped (kept live behind a never-taken branch)
-        if (acc[0][0][0] == 1.2345e-30f)
-            ep(acc, t * HB + wm * 64, n0 + wn * 64, lane, wm, wn, reinterpret_cast<float*>(Hs + (hb ^ 1) * NS * HPLANE),
-               tid);
-    } else
-        ep(acc, t * HB + wm * 64, n0 + wn * 64, lane, wm, wn, reinterpret_cast<float*>(Hs + (hb ^ 1) * NS * HPLANE), tid);
+    ep(acc, t * HB + wm * 64, n0 + wn * 64, lane, wm, wn, reinterpret_cast<float*>(Hs + (hb ^ 1) * NS * HPLANE), tid);
     if (nextt) __syncthreads();
     }
 }
@@ -2584,50 +2309,28 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_row_kernel(const GT* __restri
     }
 }
 
-// tiles per block of the LDS-halo conv (round 3: one round of 256 blocks, up to 16 tiles; round 2: >= 512 blocks, at most 8).  Kernel level
-// (tools/conv_ablation.py, h3 128->128 @64^2, B=256, one box): 1 tile 0.872 ms, 2: 0.854, 4: 0.848, 8: 0.843,
-// 16: 0.834.  Bench, same box, 2 runs each (tpb 1 -> this policy): C2 train 4296 -> 4355 img/s, sampling 15.94 ->
-// 15.71 ms per step (CFG 31.95 -> 31.50), C4 bf16 train 6416 -> 6478, sample 9.69 -> 9.46 ms, C5 train 70.7 ->
-// 71.2 img/s, sample 69.4 -> 67.6 ms.  The tiles of a block are interleaved across its XCD (see the kernel).
-static int halo_tpb(int mtiles, int ntiles, int nterm, int wt) {
-    (void)nterm; (void)wt;
-    static const int forced = [] { const char* e = getenv("CDM_HALO_TPB"); return e ? atoi(e) : 0; }();
-    if (forced > 0) return forced;   // A/B timing override (tools), never set by the product
-    // the block count the tiles are dealt to: 256 = one round of one block per CU (up to 16 tiles per block).  Same-box
-    // A/B, 2 rounds (profiles/r3_ab_grid_blocks.txt): vs 512 (two rounds, up to 8 tiles) C2 train step 51.32 -> 51.13 ms,
-    // C4 31.82 -> 31.70 ms ($CDM_HALO_BLOCKS overrides)
-    static const int blocks = [] { const char* e = getenv("CDM_HALO_BLOCKS"); return e ? atoi(e) : 256; }();
-    const int maxt = blocks <= 256 ? 16 : 8;
-    const int t = (mtiles * ntiles) / (blocks > 0 ? blocks : 512);
-    return t < 1 ? 1 : (t > maxt ? maxt : t);
+// tiles per block of the LDS-halo conv: the tiles are dealt to 256 blocks (one round of one block per CU), at most 16
+// tiles per block (round 2: >= 512 blocks, at most 8; same-box A/B, profiles/r3_ab_grid_blocks.txt: C2 train step
+// 51.32 -> 51.13 ms, C4 31.82 -> 31.70 ms).  Kernel level (h3 128->128 @64^2, B=256, one box): 1 tile 0.872 ms,
+// 2: 0.854, 4: 0.848, 8: 0.843, 16: 0.834.  Bench, same box, 2 runs each (tpb 1 -> this policy): C2 train 4296 -> 4355
+// img/s, sampling 15.94 -> 15.71 ms per step (CFG 31.95 -> 31.50), C4 bf16 train 6416 -> 6478, sample 9.69 -> 9.46 ms,
+// C5 train 70.7 -> 71.2 img/s, sample 69.4 -> 67.6 ms.  The tiles of a block are interleaved across its XCD (see the
+// kernel).
+static int halo_tpb(int mtiles, int ntiles) {
+    const int t = (mtiles * ntiles) / 256;
+    return t < 1 ? 1 : (t > 16 ? 16 : t);
 }
 
-// the staggered halo split of the LDS-halo conv: on for h3, off for the one-term bf16 images ($CDM_HALO_STAGGER=0 / 1
-// forces it).  Same-box A/B, 2 rounds (profiles/r3_ab_halo_stagger.txt): C2 (h3) train step 51.92-51.95 -> 51.34-51.44
-// ms; C4 (bf16) 32.20-32.21 -> 32.26-32.40 ms (its halo split is a plain conversion: nothing left to hide)
-static int halo_stagger(int nterm) {   // default on for h3 and (round 4, profiles/r4_ab_c4_knobs.txt) for bf16
+// the staggered halo split of the LDS-halo conv: on for h3 and (round 4, profiles/r4_ab_c4_knobs.txt) for the one-term
+// bf16 images, off for x3 / x6 ($CDM_HALO_STAGGER=0 / 1 forces it).  Same-box A/B, 2 rounds
+// (profiles/r3_ab_halo_stagger.txt): C2 (h3) train step 51.92-51.95 -> 51.34-51.44 ms
+static int halo_stagger(int nterm) {
     static const int v = [] { const char* e = getenv("CDM_HALO_STAGGER"); return e ? atoi(e) : -1; }();
     // + the block start delay (bits 8+, 10 ns ticks; $CDM_HALO_DELAY)
     static const int d = [] { const char* e = getenv("CDM_HALO_DELAY"); return e ? atoi(e) : 0; }();
-    // + static priority 1 for waves 4-7 (bit 1; $CDM_HALO_PRIO, measured neutral: off, profiles/r6_ab_wave_priority.txt).
-    // (B fetched one kernel row earlier is compiled in since round 6: as a runtime switch, bit 2, it had measured
-    // sampling 13.37-13.40 -> 13.15-13.18 ms per step, profiles/r6_ab_halo_bearly.txt; as a constant a further 13.08-13.20
-    // -> 12.87-12.95 and C2 45.10-45.31 -> 44.72-44.83 ms, profiles/r6_ab_halo_bearly_const.txt — the switch's second
-    // load site and its branches had cost that much)
+    // + static priority 1 for waves 4-7 (bit 1; $CDM_HALO_PRIO, measured neutral: off, profiles/r6_ab_wave_priority.txt)
     static const int p = [] { const char* e = getenv("CDM_HALO_PRIO"); return e ? atoi(e) : 0; }();
     return (v >= 0 ? v : ((nterm == NT_H3 || nterm == 1) ? 1 : 0)) | (p ? 2 : 0) | (d << 8);
-}
-
-// the one-barrier-per-chunk schedule of the one-term (bf16) LDS-halo conv ($CDM_HALO_ONEB=0: three barriers per chunk)
-static int halo_oneb() {
-    static const int v = [] { const char* e = getenv("CDM_HALO_ONEB"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
-static int halo_oneb_bwd() {   // the bf16 BN-backward dgrad, one barrier per chunk: default on since round 4 (bf16
-                               // g / y; profiles/r4_ab_c4_knobs.txt)
-    static const int v = [] { const char* e = getenv("CDM_HALO_ONEB_BWD"); return e ? atoi(e) : 1; }();
-    return v;
 }
 
 // the two-chunk-deep halo prefetch of the one-term forward halo conv ($CDM_HALO_DEEP=0: one chunk ahead)
@@ -2651,7 +2354,7 @@ static int launch_conv_halo(const XT* x, int N, int H, int Cin, int ldx, const _
         if ((unsigned long long)M * (unsigned)pre.ldy * sizeof(XT) >= (1ull << 32)) return (int)hipErrorInvalidValue;
     }
     if (!F32 && nterm != 1) return (int)hipErrorInvalidValue;
-    if (tpb < 1) tpb = halo_tpb(mtiles, (Cout + GBN - 1) / GBN, nterm, WT);
+    if (tpb < 1) tpb = halo_tpb(mtiles, (Cout + GBN - 1) / GBN);
     dim3 grid((mtiles + tpb - 1) / tpb, (Cout + GBN - 1) / GBN, 1);
     if constexpr (WT > 64) {
         // wide rows (C5: 128 / 256 columns): a block is 256 / WT whole rows, halo (256/WT + 2) x (WT + 2);
@@ -2660,7 +2363,7 @@ static int launch_conv_halo(const XT* x, int N, int H, int Cin, int ldx, const _
             return (int)hipErrorInvalidValue;
         } else {
             if (nterm != NT_H3) return (int)hipErrorInvalidValue;
-            hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, 1, PRE>), grid, dim3(HTHREADS), 0, s,
+            hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s,
                                x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
             return cdm_status();
         }
@@ -2668,31 +2371,28 @@ static int launch_conv_halo(const XT* x, int N, int H, int Cin, int ldx, const _
     switch (nterm) {
         case 1:
             if constexpr (!PRE::on) {
-                if (halo_oneb() && halo_deep() && Cin % 32 == 0) {
-                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, 1 | 2048 | 4096, PRE, XT>),
+                if (halo_deep() && Cin % 32 == 0) {
+                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, true, true, PRE, XT>),
                                        grid, dim3(HTHREADS), 0, s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre,
                                        mtiles, tpb, halo_stagger(nterm));
                     break;
                 }
             }
-            // (the BN-backward staging form spills 12 VGPRs with the 9-tap B set: one barrier per chunk only by request)
-            if (PRE::on ? halo_oneb_bwd() : halo_oneb())
-                hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, 1 | 2048, PRE, XT>), grid, dim3(HTHREADS),
-                                   0, s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
-            else
-                hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, 1, PRE, XT>), grid, dim3(HTHREADS), 0, s,
-                                   x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
+            // one barrier per chunk (the BN-backward staging form too, since round 4: bf16 g / y,
+            // profiles/r4_ab_c4_knobs.txt)
+            hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, true, false, PRE, XT>), grid, dim3(HTHREADS), 0,
+                               s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
             break;
         default:
             if constexpr (F32) {
                 if (nterm == NT_H3) {
-                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, 1, PRE>), grid, dim3(HTHREADS), 0,
+                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0,
                                        s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
                 } else if constexpr (!FUSE) {   // the x3 / x6 arithmetics: no fused eval epilogue
                     switch (nterm) {
-                        case 3: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<3, WT, EP, true, 1, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
+                        case 3: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
                                                    Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm)); break;
-                        case 6: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<6, WT, EP, true, 0, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
+                        case 6: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<6, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
                                                    Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm)); break;
                         default: return (int)hipErrorInvalidValue;
                     }

@@ -332,21 +332,8 @@ CDM_API int cdm_convT2x2_fwd_x16(const float* x, int N, int H, int W, int Cin, i
         (nterm == NT_H3 || nterm == 1)) {
         const dim3 grid(M / GBM, NN / GBN);
         const __bf16* wb = reinterpret_cast<const __bf16*>(wx);
-        // transposed accumulators + 16-byte scatter stores ($CDM_CONVT_TRO=1; needs 16-byte aligned output rows and
-        // whole 8-column groups per sub-pixel): bit-identical but 213 -> 219 us per launch in the sampling step and C2
-        // +0.15 ms (profiles/r6_ab_convT_tro.txt) — the dword-store epilogue was not store-issue bound; off
-        static const int tro_env = [] { const char* e = getenv("CDM_CONVT_TRO"); return e ? atoi(e) : 0; }();
-        const bool tro = tro_env && Cout % 8 == 0 && ldy % 4 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0;
-        if (tro) {
-            const EpiConvT2x2T et{y, ldy, bias, H, W, Cout, M, NN, amax_y};
-            if (nterm == NT_H3)
-                hipLaunchKernelGGL((gemm_deep_kernel<NT_H3, DeepDenseA, EpiConvT2x2T, 3, true>), grid, dim3(GTHREADS), 0,
-                                   S(stream), DeepDenseA{x, ldx}, wb, NN, amax_x, amax_w, et, K);
-            else
-                hipLaunchKernelGGL((gemm_deep_kernel<1, DeepDenseA, EpiConvT2x2T, 3, true>), grid, dim3(GTHREADS), 0,
-                                   S(stream), DeepDenseA{x, ldx}, wb, NN, amax_x, amax_w, et, K);
-            return cdm_status();
-        }
+        // (transposed accumulators + 16-byte scatter stores measured bit-identical but slower, 213 -> 219 us per launch
+        // in the sampling step: the dword-store epilogue is not store-issue bound, profiles/r6_ab_convT_tro.txt)
         if (nterm == NT_H3)
             hipLaunchKernelGGL((gemm_deep_kernel<NT_H3, DeepDenseA, EpiConvT2x2, 3>), grid, dim3(GTHREADS), 0,
                                S(stream), DeepDenseA{x, ldx}, wb, NN, amax_x, amax_w, ep, K);
@@ -431,11 +418,10 @@ CDM_API int cdm_convT2x2_wgrad_x16(const float* x, int N, int H, int W, int Cin,
     const int M = Cin, NN = 4 * Cout, K = N * H * W;
     const int sp = effective_splits(K, splits);
     EpiStore ep{slab, NN, (long long)M * NN, nullptr, 1, 0, nullptr, 0, M, NN};
-    static const bool tr = [] { const char* e = getenv("CDM_CONVT_WGRAD_TR"); return !e || atoi(e) != 0; }();
-    if (tr && Cin % 128 == 0 && Cout % 128 == 0 && W % 16 == 0 && ldx % 4 == 0 && lddy % 4 == 0 &&
+    if (Cin % 128 == 0 && Cout % 128 == 0 && W % 16 == 0 && ldx % 4 == 0 && lddy % 4 == 0 &&
         effective_splits(K, splits, 16) == sp) {
-        // the transposed-read staging of the 3x3 weight gradient with the ConvT sub-pixel map ($CDM_CONVT_WGRAD_TR=0:
-        // the generic GEMM below)
+        // the transposed-read staging of the 3x3 weight gradient with the ConvT sub-pixel map (other shapes: the generic
+        // GEMM below)
         const int ktiles = K / 16, per = (ktiles + sp - 1) / sp;
         dim3 grid((M / GBM) * (NN / GBN) * ((ktiles + per - 1) / per));
         if (nterm == NT_H3)

@@ -389,20 +389,20 @@ __global__ __launch_bounds__(256) void conv_cin1_dgrad_kernel(const float* g1, i
 // HPM: halo pixels the LDS images hold, (R + 2) W rounded up to 64: 384 for W <= 64 (40 KiB of LDS, 4 blocks per CU;
 // the W-independent 768-pixel images took 80 KiB, 2 blocks per CU, half the loads in flight: 2.3 TB/s), 512 for W = 128,
 // 768 for W = 256
-// FULL = false (default): 256 threads, up to HPM / 256 halo pixels per thread in the tap reduction (at 384 pixels the
-// SIMDs holding waves 0-1 do twice the FMAs of the others).  FULL ($CDM_COUT1_FULL=1): HPM threads, one halo pixel
-// each — balanced SIMDs, but same-box 182 vs 164 us per C2 step (profiles/r4_ab_cout1_threads.txt)
+// 256 threads, up to HPM / 256 halo pixels per thread in the tap reduction (at 384 pixels the SIMDs holding waves 0-1
+// do twice the FMAs of the others; HPM threads with one halo pixel each measured slower, same-box 182 vs 164 us per
+// C2 step, profiles/r4_ab_cout1_threads.txt)
 // SL: channels per LDS slab, 16 (default) or 32 ($CDM_COUT1_SLAB=32, C % 32 == 0: a pixel's slab piece is then one
 // whole 128-byte line — measured no faster, 144-149 vs 137-160 us at the bench shape, profiles/r5_cout1_probe.jsonl).
 // The tap partials st alias the slab image once the last slab is reduced (LDS 26 KiB at SL = 16).
-template <int HPM, bool FULL = true, int SL = 16>
-__global__ __launch_bounds__(FULL ? HPM : 256) void conv_cout1_fwd_band_kernel(const float* __restrict__ z, int ldz, int H, int W,
+template <int HPM, int SL = 16>
+__global__ __launch_bounds__(256) void conv_cout1_fwd_band_kernel(const float* __restrict__ z, int ldz, int H, int W,
                                                                   int C, const float* __restrict__ w,
                                                                   const float* __restrict__ bias,
                                                                   float* __restrict__ out,
                                                                   const float* __restrict__ gs,
                                                                   const float* __restrict__ gt) {
-    constexpr int NTHR = FULL ? HPM : 256;
+    constexpr int NTHR = 256;
     constexpr int KQ = (HPM + NTHR - 1) / NTHR;       // halo pixels per thread in the tap reduction
     constexpr int PPX = SL / 4;                       // float4 pieces per halo pixel and slab
     constexpr int ZT = HPM * (SL + 1), STN = 9 * HPM;
@@ -498,7 +498,6 @@ __global__ __launch_bounds__(FULL ? HPM : 256) void conv_cout1_fwd_band_kernel(c
     }
     __syncthreads();
     // output pixel (h0 + r, c): sum over taps of the partial of halo pixel (r + ky, c + kx - 1)
-    if (FULL && tid >= 256) return;
     const int r = tid / W, c = tid - r * W;
     float o = bias[0];
 #pragma unroll
@@ -1169,31 +1168,21 @@ static int launch_cout1_band(const float* z, int ldz, int N, int H, int W, int C
                              float* out, const float* gs, const float* gt, hipStream_t st) {
     const dim3 grid(N * (H / (256 / W)));
     const int hp = (256 / W + 2) * W;           // halo pixels of a band
-    static const int full = [] { const char* e = getenv("CDM_COUT1_FULL"); return e ? atoi(e) : 0; }();
     // 32-channel slabs on request ($CDM_COUT1_SLAB=32, read per call for A/B tests; not for 768-pixel bands: spills)
     const char* sv = getenv("CDM_COUT1_SLAB");
-    if (!full && C % 32 == 0 && hp <= 512 && sv && atoi(sv) == 32) {
+    if (C % 32 == 0 && hp <= 512 && sv && atoi(sv) == 32) {
         if (hp <= 384)
-            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<384, false, 32>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
+            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<384, 32>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
         else
-            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<512, false, 32>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
-        return cdm_status();
-    }
-    if (!full) {
-        if (hp <= 384)
-            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<384, false>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
-        else if (hp <= 512)
-            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<512, false>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
-        else
-            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<768, false>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
+            hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<512, 32>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
         return cdm_status();
     }
     if (hp <= 384)
-        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<384>, grid, dim3(384), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
+        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<384>, grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
     else if (hp <= 512)
-        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<512>, grid, dim3(512), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
+        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<512>, grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
     else
-        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<768>, grid, dim3(768), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
+        hipLaunchKernelGGL(conv_cout1_fwd_band_kernel<768>, grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
     return cdm_status();
 }
 CDM_API int cdm_conv3x3_cout1_fwd(const float* z, int ldz, int N, int H, int W, int C, const float* w, const float* bias,

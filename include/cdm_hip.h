@@ -72,9 +72,9 @@ int cdm_conv3x3_fwd_x16_fused(const float* x, int N, int H, int W, int Cin, int 
                               const float* amax_x, const float* amax_w, const float* bias, float* y, int ldy, int Cout,
                               int kc, float* amax_y, int kind, const float* sc_x, const float* sc_w, const float* sc_b,
                               int split, const float* fa, int fan, const float* fb, int fbn, int nterm, void* stream);
-/* timing ablations of the h3 LDS-halo conv (64x64 maps, no bias / stats; tools/conv_ablation.py): abl bits
- * 1 fragment prefetch, 2 MFMAs doubled, 4 B staged once, 8 halo without the term split (results meaningless);
- * bits 16+: tiles per block (0 -> 1) */
+/* tiles-per-block hook of the shipped h3 LDS-halo conv (64x64 maps, no bias / stats; tests): the low 16 bits of abl
+ * must be 1 (the retired timing-ablation masks return hipErrorInvalidValue and launch nothing); bits 16+: tiles per
+ * block (0 -> 1) in place of the launcher's own policy */
 int cdm_conv3x3_halo_ablate(int abl, const float* x, int N, int H, int Cin, int ldx, const void* wx,
                             const float* amax_x, const float* amax_w, float* y, int ldy, int Cout, void* stream);
 int cdm_conv3x3_wgrad_h3(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin, int ldx,

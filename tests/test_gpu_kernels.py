@@ -504,8 +504,9 @@ def test_deep_staging_bit_exact(L, tmp_path):
     the flat-pixel kernels bit for bit ($CDM_ROW_KERNELS), and the fused weight gradients are reproducible across
     processes: two child processes (tests/_variant_worker.py), the library reading the switches once per process.
     Round 6: the second process also runs the previous schedules — the lock-step weight gradient ($CDM_WGRAD_STAGGER=0),
-    the halo B fetched in the last kernel row ($CDM_HALO_BEARLY=0), the ConvT input gradient at three blocks per CU
-    ($CDM_CONVT_DGRAD_MINB=3) — which must give the same bits (slabs, producer BN sums, outputs, statistics)."""
+    the ConvT input gradient at three blocks per CU ($CDM_CONVT_DGRAD_MINB=3) — which must give the same bits (slabs,
+    producer BN sums, outputs, statistics).  The h3 halo forward has no switch left (its B fetch one kernel row earlier
+    is compiled in): its output and statistics show that it is reproducible across processes."""
     import subprocess
     import sys
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_variant_worker.py")
@@ -514,7 +515,7 @@ def test_deep_staging_bit_exact(L, tmp_path):
         f = tmp_path / f"deep{deep}.pt"
         env = dict(os.environ, CDM_HALO_DEEP=deep, CDM_ROW_KERNELS=deep)
         if deep == "0":
-            env.update(CDM_WGRAD_STAGGER="0", CDM_HALO_BEARLY="0", CDM_CONVT_DGRAD_MINB="3")
+            env.update(CDM_WGRAD_STAGGER="0", CDM_CONVT_DGRAD_MINB="3")
         r = subprocess.run([sys.executable, worker, str(f)], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(torch.load(f))
@@ -541,6 +542,34 @@ def test_halo_conv_tiles_per_block_bit_exact(L, N, tpb):
     for out, t in ((ref, 1), (got, tpb)):
         assert L.cdm_conv3x3_halo_ablate(1 | (t << 16), x.data_ptr(), N, H, C, C, wx.data_ptr(), amx.data_ptr(),
                                          amw.data_ptr(), out.data_ptr(), C, C, _s()) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(ref).all()
+    assert torch.equal(got, ref)
+
+
+def test_halo_conv_tiles_per_block_hook_rejects_retired_masks(L):
+    """cdm_conv3x3_halo_ablate is the tiles-per-block hook of the shipped h3 kernel only: the retired ablation masks (low
+    16 bits other than 1) return an error and leave y untouched; low bits 1 with one tile per block equal
+    cdm_conv3x3_fwd_h3 on the same operands bit for bit."""
+    N, H, C = 1, 64, 128
+    g_ = torch.Generator(device="cuda").manual_seed(12)
+    P = N * H * H
+    x = torch.randn(P, C, device="cuda", generator=g_).relu()
+    W = torch.randn(9 * C, C, device="cuda", generator=g_) * 0.05
+    wx, amw = _split_h3(L, W, 9 * C, C)
+    amx = _amax(L, x, P, C)
+    for low in (0, 3):
+        y = torch.full((P, C), -7.5, device="cuda")
+        # (the unchecked entry: the bound one raises on a non-zero return)
+        assert L.raw("cdm_conv3x3_halo_ablate")(low | (1 << 16), x.data_ptr(), N, H, C, C, wx.data_ptr(), amx.data_ptr(),
+                                                amw.data_ptr(), y.data_ptr(), C, C, _s()) != 0
+        torch.cuda.synchronize()
+        assert torch.equal(y, torch.full_like(y, -7.5)), low
+    got = torch.full((P, C), float("nan"), device="cuda"); ref = torch.full_like(got, float("nan"))
+    assert L.cdm_conv3x3_halo_ablate(1 | (1 << 16), x.data_ptr(), N, H, C, C, wx.data_ptr(), amx.data_ptr(),
+                                     amw.data_ptr(), got.data_ptr(), C, C, _s()) == 0
+    assert L.cdm_conv3x3_fwd_h3(x.data_ptr(), N, H, H, C, C, wx.data_ptr(), amx.data_ptr(), amw.data_ptr(), None,
+                                ref.data_ptr(), C, C, 0, None, 0, 16, None, _s()) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(ref).all()
     assert torch.equal(got, ref)

@@ -1,8 +1,8 @@
-"""A/B bit-exactness of a kernel-variant knob over whole train steps: runs the bench's seeded train step (graph-replayed)
-for a few steps and writes every parameter (after the optimizer steps) to an npz; compare two runs made under two
-environment settings:
-  CDM_HALO_TALL=0 python tools/tall_check.py --out a.npz --math bf16
-  CDM_HALO_TALL=1 python tools/tall_check.py --out b.npz --math bf16
+"""Generic two-run bit comparison over whole train steps: runs the bench's seeded train step (graph-replayed) for a few
+steps and writes every parameter (after the optimizer steps) to an npz; compare two runs made with two libraries
+($CDM_LIB) or under two settings of a kernel-variant switch the library reads (DESIGN.md lists them):
+  CDM_LIB=lib/ab/a/libcdm_hip.so python tools/tall_check.py --out a.npz --math bf16
+  CDM_LIB=lib/ab/b/libcdm_hip.so python tools/tall_check.py --out b.npz --math bf16
   python tools/tall_check.py --cmp a.npz b.npz"""
 import argparse
 import os
