@@ -1026,6 +1026,48 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long l
         m[i] = mi; v[i] = vi;
     }
 }
+// adam_kernel + the exponential moving average of the parameters in the same pass (p is in registers: a separate EMA
+// kernel would read the 86.5 MB of p again).  The Adam expressions are adam_kernel's, line for line, under the same
+// contract(off): p, m, v come out bit-identical.  ema += (1 - decay) (p_new - ema) as one fmaf; decay is a device
+// double (like lr in state), so a captured step follows set_ema_decay without re-capture.  decay == 0 copies p:
+// fl(fl(p - e) + e) is not always p (p - e is inexact once |p| falls to the size of an update).
+__global__ void adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,
+                                const double* ema_decay, float beta1c, float beta2, float beta2c, float eps, float gscale) {
+#pragma clang fp contract(off)  // only the explicit fmaf below fuse, as in torch's CPU kernels
+    const float nss = (float)state[2], bc2s = (float)state[3];
+    const float omd = (float)(1.0 - *ema_decay);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * gscale;
+        float mi = m[i];
+        mi = fmaf(beta1c, gi - mi, mi);
+        float vi = v[i] * beta2;
+        vi = fmaf(beta2c * gi, gi, vi);
+        const float denom = sqrtf(vi) / bc2s + eps;
+        const float pn = p[i] + (nss * mi) / denom;
+        p[i] = pn;
+        m[i] = mi; v[i] = vi;
+        const float ei = ema[i];
+        ema[i] = omd == 1.0f ? pn : fmaf(omd, pn - ei, ei);
+    }
+}
+
+// Context dropout for classifier-free guidance: c_out[b][:] = u[b] < p_drop ? 0 : c[b][:], u[b] element b of the
+// stream philox_uniform_kernel(out, B, 0, 1, seed, sub, sub_dev) writes (lo + (hi - lo) u01 is u01 itself there).
+// keep (optional) [B]: 1 where the row was kept.
+__global__ void context_drop_kernel(const float* c, int B, int ncf, float p_drop, unsigned long long seed, uint32_t sub,
+                                    const int* sub_dev, float* c_out, int* keep) {
+    if (sub_dev) sub += (uint32_t)*sub_dev;
+    const long long total = (long long)B * ncf;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / ncf), f = (int)(i - (long long)b * ncf);
+        const U4 r = philox((uint32_t)(b >> 2), 0u, sub, 0x0417u, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const int j = b & 3;
+        const float u = u01(j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w)));
+        const bool drop = u < p_drop;
+        c_out[i] = drop ? 0.f : c[i];
+        if (keep && f == 0) keep[b] = drop ? 0 : 1;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // weight packing
@@ -1334,6 +1376,24 @@ CDM_API int cdm_adam(float* p, const float* g, float* m, float* v, long long n, 
     int e = cdm_status(); if (e) return e;
     hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n, 256, 16384)), dim3(256), 0, S(stream), p, g, m, v, n, state,
                        (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, grad_scale);
+    return cdm_status();
+}
+CDM_API int cdm_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state,
+                         const double* bc, int nbc, double beta1, double beta2, double eps, float grad_scale,
+                         const double* ema_decay, void* stream) {
+    if (nbc < 1 || n < 0 || !ema || !ema_decay) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, S(stream), state, bc, nbc);
+    int e = cdm_status(); if (e || n == 0) return e;
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(nblocks(n, 256, 16384)), dim3(256), 0, S(stream), p, g, m, v, ema, n, state,
+                       ema_decay, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, grad_scale);
+    return cdm_status();
+}
+CDM_API int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsigned long long seed, unsigned int sub,
+                             const int* sub_dev, float* c_out, int* keep, void* stream) {
+    if (!(p_drop >= 0.f && p_drop <= 1.f) || B < 1 || ncf < 1 || !c || !c_out || c == c_out)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(context_drop_kernel, dim3(nblocks((long long)B * ncf)), dim3(256), 0, S(stream), c, B, ncf, p_drop,
+                       seed, sub, sub_dev, c_out, keep);
     return cdm_status();
 }
 CDM_API int cdm_pack_conv3x3(const float* W, const float* b, int Cin, int Cout, const float* gamma, const float* beta,

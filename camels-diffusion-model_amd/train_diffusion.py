@@ -24,10 +24,20 @@ The CAMELS files are not in this repository (Git-LFS stubs upstream): pass --dat
 to train on synthetic maps of the same shape.
 Plots of the reference (loss curves, PDFs, P(k)) are analysis, outside the hot path: losses, samples and
 timings are written as .npy / .log instead.
+
+Training for guided sampling (all off by default; without them the outputs are those described above):
+  --p-uncond P   each sample's context is replaced by the null condition c = 0 with probability P in a step, so the
+                 c = 0 forward of classifier-free guidance (--guide-w > 0) is one the model was trained on.
+  --ema DECAY    keep an exponential moving average of the parameters; the sampling at the end runs on it, and every
+                 model_epoch_N.pth gets a model_epoch_N_ema.pth beside it.
+  --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
+                 epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
+                 the epoch after the one it was written in, with that epoch's learning rate.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -58,6 +68,10 @@ def main(argv=None):
     ap.add_argument("--guide-w", type=float, default=0.0)
     ap.add_argument("--no-sample", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--p-uncond", type=float, default=0.0, help="context dropout probability (train the c = 0 branch)")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep and sample from EMA weights")
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="write trainer_epoch_N.pt checkpoints; continue from PATH if it exists")
     a = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
@@ -112,11 +126,23 @@ def main(argv=None):
     # ------------------------------- model / trainer -------------------------------
     torch.manual_seed(a.seed)
     model = ContextUnet(1, a.n_feat, n_cfeat, H).to(dev)
-    trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed)
+    trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed, ema_decay=a.ema, p_uncond=a.p_uncond)
     log = open(os.path.join(out_dir, "timing_and_performance.log"), "a") if rank == 0 else None
     loss_log, val_log = [], []
+    first_ep = 0
+    if a.resume is not None:
+        if os.path.isfile(a.resume):
+            ck = torch.load(a.resume, map_location="cpu", weights_only=True)
+            trainer.load_state_dict(ck["trainer"])
+            first_ep, loss_log, val_log = int(ck["epoch"]), list(ck["loss_log"]), list(ck["val_log"])
+            msg = f"Resumed from {a.resume}: epoch {first_ep} done, {trainer.steps} steps"
+        else:
+            msg = f"No checkpoint at {a.resume}: starting at epoch 1"
+        if rank == 0:
+            print(msg, flush=True)
+            log.write(msg + "\n")
     t_train0 = time.time()
-    for ep in range(a.epochs):
+    for ep in range(first_ep, a.epochs):
         t_ep = time.time()
         lr = a.lr * (1 - ep / a.epochs)
         trainer.set_lr(lr)
@@ -149,6 +175,13 @@ def main(argv=None):
             if save_now:
                 name = f"model_epoch_{ep + 1}.pth" if conditional else f"model_epoch_{ep}.pth"
                 torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(save_dir, name))
+                n_ep = name[len("model_epoch_"):-len(".pth")]
+                if a.ema is not None:
+                    torch.save({k: v.cpu() for k, v in trainer.ema_state_dict().items()},
+                               os.path.join(save_dir, f"model_epoch_{n_ep}_ema.pth"))
+                if a.resume is not None:
+                    torch.save({"trainer": trainer.state_dict(), "epoch": ep + 1, "loss_log": loss_log,
+                                "val_log": val_log}, os.path.join(save_dir, f"trainer_epoch_{n_ep}.pt"))
     total_train = time.time() - t_train0
     if rank == 0:
         np.save(os.path.join(out_dir, "loss_log.npy"), np.array(loss_log))
@@ -158,41 +191,50 @@ def main(argv=None):
 
     # ------------------------------- sampling -------------------------------
     if not a.no_sample and rank == 0:
-        model.eval()
-        d = DDPM(model, a.timesteps, dev)
-        ns = a.n_samples
-        src = test_idx if len(test_idx) else torch.arange(min(ns, n_total))
-        sel = src[:ns].to(dev)
-        x = maps_d[sel]
-        p = params_d[sel] if conditional else None
-        noise = torch.randn(x.shape, device=dev)
-        x_T = cdm_amd.perturb_input(x, a.timesteps, noise, d.sched)
-        t0 = time.time()
-        rec, inter = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w)
-        torch.cuda.synchronize()
-        dt = time.time() - t0
-        np.save(os.path.join(out_dir, "reconstructed_images.npy"), rec.cpu().numpy())
-        np.save(os.path.join(out_dir, "intermediate.npy"), inter)
-        log.write(f"Reconstruction of {ns} maps, T={a.timesteps}: {dt:.2f} s\n")
-        # the reference's post-sampling statistics (code/train_diffusion.py:250, diffusion_utilities.py:370),
-        # on the HIP statistics kernels; the plotted arrays go to .npz files
-        cdm_amd.compare_distributions(x[:, 0].cpu().numpy(), rec[:, 0].cpu().numpy(), out_dir)
-        cdm_amd.compare_power_spectra(x, rec, out_dir)
-        if conditional:
-            t0 = time.time()
-            samples, _ = d.sample_ddpm(ns, H, dev, p, a.guide_w)
-            torch.cuda.synchronize()
-            dt = time.time() - t0
-            np.save(os.path.join(out_dir, "generated_samples.npy"), samples.cpu().numpy())
-            log.write(f"Sampling {ns} maps (w={a.guide_w}), T={a.timesteps}: {dt:.2f} s ({ns / dt:.3f} img/s)\n")
-        with open(os.path.join(out_dir, "means.txt"), "w") as f:
-            f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
+        # --ema: sample from the averaged weights; the live ones return afterwards
+        with trainer.ema_weights() if a.ema is not None else contextlib.nullcontext():
+            sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditional, dev, H, out_dir, log)
     if log:
         log.close()
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     return out_dir
+
+
+def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditional, dev, H, out_dir, log):
+    """The reference's post-training sampling (code/train_diffusion.py:163-193, train_diffusion_condition.py:301-333)."""
+    import cdm_amd
+    from cdm_amd import DDPM
+    model.eval()
+    d = DDPM(model, a.timesteps, dev)
+    ns = a.n_samples
+    src = test_idx if len(test_idx) else torch.arange(min(ns, n_total))
+    sel = src[:ns].to(dev)
+    x = maps_d[sel]
+    p = params_d[sel] if conditional else None
+    noise = torch.randn(x.shape, device=dev)
+    x_T = cdm_amd.perturb_input(x, a.timesteps, noise, d.sched)
+    t0 = time.time()
+    rec, inter = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    np.save(os.path.join(out_dir, "reconstructed_images.npy"), rec.cpu().numpy())
+    np.save(os.path.join(out_dir, "intermediate.npy"), inter)
+    log.write(f"Reconstruction of {ns} maps, T={a.timesteps}: {dt:.2f} s\n")
+    # the reference's post-sampling statistics (code/train_diffusion.py:250, diffusion_utilities.py:370),
+    # on the HIP statistics kernels; the plotted arrays go to .npz files
+    cdm_amd.compare_distributions(x[:, 0].cpu().numpy(), rec[:, 0].cpu().numpy(), out_dir)
+    cdm_amd.compare_power_spectra(x, rec, out_dir)
+    if conditional:
+        t0 = time.time()
+        samples, _ = d.sample_ddpm(ns, H, dev, p, a.guide_w)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        np.save(os.path.join(out_dir, "generated_samples.npy"), samples.cpu().numpy())
+        log.write(f"Sampling {ns} maps (w={a.guide_w}), T={a.timesteps}: {dt:.2f} s ({ns / dt:.3f} img/s)\n")
+    with open(os.path.join(out_dir, "means.txt"), "w") as f:
+        f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 
 
 @torch.no_grad()

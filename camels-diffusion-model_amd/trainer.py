@@ -10,6 +10,10 @@ MI355X design:
   * noise / timesteps / the per-forward random 1x1 shortcut come from on-device Philox keyed by a
     device step counter, so the whole step (repack -> forward -> mse -> backward -> Adam) is captured
     once in a hipGraph and replayed (single GPU);
+  * optional, off by default (training for classifier-free guidance): context dropout (p_uncond: each sample's
+    context is zeroed with that probability, one more Philox draw inside the step), an exponential moving average of
+    the parameters kept by the fused Adam kernel (ema_decay; ema_weights() / ema_state_dict() to sample from it), and
+    state_dict() / load_state_dict() that continue a run bit-identically;
   * data parallel: one process per GPU; each rank trains on its own shard of the global batch; the
     flat gradient buffer is laid out in backward-completion order and cut into stage buckets that are
     all-reduced (RCCL over xGMI) asynchronously as soon as the engine reports a stage complete, so the
@@ -19,6 +23,7 @@ MI355X design:
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -80,9 +85,18 @@ class GradBucketer:
 
 class Trainer:
     def __init__(self, model, lrate: float, timesteps: int, batch_size: int, seed: int = 0,
-                 use_graph: bool = True, group=None, broadcast_buffers: bool = True, force_ddp: bool = False):
+                 use_graph: bool = True, group=None, broadcast_buffers: bool = True, force_ddp: bool = False,
+                 ema_decay: Optional[float] = None, p_uncond: float = 0.0):
         """``force_ddp``: take the data-parallel path (stage-bucketed async all-reduce, rank-0 broadcasts, eager
-        steps) even in a one-rank process group — RCCL readiness on a one-GPU box (tests/test_gpu_rccl.py)."""
+        steps) even in a one-rank process group — RCCL readiness on a one-GPU box (tests/test_gpu_rccl.py).
+        ``ema_decay``: keep ``self.ema``, an exponential moving average of the parameters, updated inside the fused
+        Adam kernel (ema += (1 - decay) (p - ema) after every step; starts as a copy of the parameters).
+        ``p_uncond``: probability with which a sample's context is replaced by the null condition c = 0 in a step
+        (the condition the guided samplers evaluate; the reference never trains it)."""
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1], got {ema_decay}")
+        if not 0.0 <= float(p_uncond) <= 1.0:
+            raise ValueError(f"p_uncond must lie in [0, 1], got {p_uncond}")
         self.model = model
         eng, P = model._engine_and_params()
         self.eng = eng
@@ -107,6 +121,7 @@ class Trainer:
         self.views: Dict[str, torch.Tensor] = {}
         self.grads: Dict[str, torch.Tensor] = {}
         self.ranges: Dict[str, Tuple[int, int]] = {}
+        self.offsets: Dict[str, int] = {}
         off = 0
         for st, grp in order:
             lo = off
@@ -118,6 +133,7 @@ class Trainer:
                 p.data = view
                 self.views[n] = view
                 self.grads[n] = self.gflat[off:off + k].view_as(p)
+                self.offsets[n] = off
                 off += k
             self.ranges[st] = (lo, off)
         self.total = total
@@ -136,6 +152,11 @@ class Trainer:
             dist.broadcast(self.flat, 0, group=group)
             dist.broadcast(self.bnflat, 0, group=group)
             self.bucketer = GradBucketer(self.gflat, self.ranges, group)
+        # ---- averaged weights (after the broadcast: every rank starts from rank 0's) and context dropout ----
+        self.ema = self.flat.clone() if ema_decay is not None else None
+        self.ema_decay = None if ema_decay is None else torch.tensor([float(ema_decay)], dtype=torch.float64, device=dev)
+        self.p_uncond = float(p_uncond)
+        self._in_ema = False          # inside ema_weights(): flat holds the EMA, a step would train it
         # ---- optimizer state on device (fp64, as torch keeps lr / step as Python floats):
         #      [lr, step, -step_size, sqrt(bc2)] + the host-evaluated bias-correction table ----
         self.betas, self.eps = (0.9, 0.999), 1e-8
@@ -182,6 +203,14 @@ class Trainer:
         """optim.param_groups[0]['lr'] = lr (code/train_diffusion_condition.py:213); exact Python-float lr."""
         self.opt_state[0:1].fill_(float(lr))
 
+    def set_ema_decay(self, decay: float):
+        """New EMA decay from the next step on (a device double, like lr: captured steps follow it)."""
+        if self.ema is None:
+            raise RuntimeError("this Trainer keeps no EMA weights (ema_decay=None)")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1], got {decay}")
+        self.ema_decay.fill_(float(decay))
+
     def check_finite(self, reset: bool = True) -> int:
         """Number of steps since the last check whose loss was NaN / inf (SURVEY §5 failure guard).  One host sync:
         call it once per epoch, not per step."""
@@ -189,6 +218,91 @@ class Trainer:
         if reset and n:
             self.nonfinite.zero_()
         return n
+
+    # ---- EMA weights ---------------------------------------------------------------------------
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("this Trainer keeps no EMA weights (ema_decay=None)")
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The model's state dict with the parameters taken from the EMA (copies).  The BatchNorm buffers are the live
+        ones: running statistics are moving averages already."""
+        self._need_ema()
+        out = {}
+        for k, v in self.model.state_dict().items():
+            off = self.offsets.get(k)
+            out[k] = (v.detach() if off is None else self.ema[off:off + v.numel()].view_as(v)).clone()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the model on the EMA weights: ``with trainer.ema_weights(): DDPM(model, T).sample_ddpm(...)``.
+        The EMA is copied into the flat parameter buffer (the parameters keep their addresses, so captured steps stay
+        valid) and the live parameters are put back, bit for bit, on exit.  No training step inside the block."""
+        self._need_ema()
+        live = self.flat.clone()
+        self.flat.copy_(self.ema)
+        self.eng.invalidate()
+        self._in_ema = True
+        try:
+            yield self.model
+        finally:
+            self._in_ema = False
+            self.flat.copy_(live)
+            self.eng.invalidate()
+
+    # ---- checkpointing -------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, object]:
+        """Everything a run needs to continue bit-identically (host copies): the model's state dict (parameters and
+        BatchNorm buffers, num_batches_tracked included), the Adam moments and the EMA in the flat layout, the device
+        optimizer state [lr, step, ...], the Philox step counter and the scalar settings the draws depend on."""
+        def cpu(t):
+            return t.detach().cpu().clone()
+        return {
+            "version": 1,
+            "model": {k: cpu(v) for k, v in self.model.state_dict().items()},
+            "layout": list(self.offsets),
+            "m": cpu(self.m), "v": cpu(self.v), "ema": None if self.ema is None else cpu(self.ema),
+            "opt_state": cpu(self.opt_state), "ctr": cpu(self.ctr), "nonfinite": cpu(self.nonfinite),
+            "steps": int(self.steps), "seed": int(self.seed),
+            "ema_decay": None if self.ema is None else float(self.ema_decay.item()),
+            "p_uncond": float(self.p_uncond),
+        }
+
+    def load_state_dict(self, sd: Dict[str, object]):
+        """Continue from ``state_dict()`` output.  Every tensor is copied into the buffer the trainer already holds
+        (addresses stay: a captured step survives, unless the seed or p_uncond it was captured with changes)."""
+        if (sd.get("ema") is None) != (self.ema is None):
+            raise ValueError("the checkpoint has EMA weights and the trainer was built with ema_decay=None"
+                             if self.ema is None else
+                             "the trainer keeps EMA weights and the checkpoint has none")
+        if list(sd["layout"]) != list(self.offsets):
+            raise ValueError("checkpoint holds a different parameter list than this model")
+        own = self.model.state_dict()
+        msd = sd["model"]
+        if set(msd) != set(own):
+            raise ValueError("checkpoint holds a different state dict than this model")
+        for k, v in own.items():
+            if tuple(msd[k].shape) != tuple(v.shape):
+                raise ValueError(f"{k}: checkpoint shape {tuple(msd[k].shape)}, model {tuple(v.shape)}")
+        for k in ("m", "v", "ema"):
+            if sd[k] is not None and sd[k].numel() != self.total:
+                raise ValueError(f"{k}: checkpoint holds {sd[k].numel()} values, the trainer {self.total}")
+        if tuple(sd["opt_state"].shape) != tuple(self.opt_state.shape):
+            raise ValueError("opt_state: size mismatch")
+        with torch.no_grad():
+            for k, v in own.items():         # state_dict() tensors alias the flat buffers: in-place copies
+                v.copy_(msd[k])
+            self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+            if self.ema is not None:
+                self.ema.copy_(sd["ema"])
+                self.ema_decay.fill_(float(sd["ema_decay"]))
+            self.opt_state.copy_(sd["opt_state"]); self.ctr.copy_(sd["ctr"]); self.nonfinite.copy_(sd["nonfinite"])
+        self.steps = int(sd["steps"])
+        if int(sd["seed"]) != self.seed or float(sd["p_uncond"]) != self.p_uncond:
+            self.seed, self.p_uncond = int(sd["seed"]), float(sd["p_uncond"])
+            self.graph = None                # both are launch arguments of the captured step
+        self.eng.invalidate()
 
     def _body(self, s: int):
         lb = lib()
@@ -201,13 +315,22 @@ class Trainer:
             lb.cdm_philox_randint(_p(sb.t_int), B, 1, self.T, seed, 1 << 24, _p(self.ctr), s)
             lb.cdm_philox_uniform(_p(self.sc), 2 * nf, -1.0, 1.0, seed, 2 << 24, _p(self.ctr), s)
         else:                      # parity mode: caller-provided draws (eager only)
-            noise, t_int, sc = self._inject
+            noise, t_int, sc = self._inject[:3]
             sb.noise.copy_(noise.reshape(-1)); sb.t_int.copy_(t_int.reshape(-1))
             self.sc.copy_(sc.reshape(-1))
+        c_in = sb.c
+        if self.p_uncond > 0.0:    # context dropout: the engine reads c_eff, the caller's batch in sb.c stays intact
+            c_in = sb.c_eff
+            if self._inject is not None and len(self._inject) > 3:
+                sb.keep.copy_(self._inject[3].reshape(-1))
+                torch.where(sb.keep[:, None] != 0, sb.c, torch.zeros((), device=self.dev), out=sb.c_eff)
+            else:
+                lb.cdm_context_drop(_p(sb.c), B, self.ncf, self.p_uncond, seed, 3 << 24, _p(self.ctr), _p(sb.c_eff),
+                                    _p(sb.keep), s)
         lb.cdm_perturb(_p(sb.x0), _p(sb.noise), _p(sb.t_int), None, 0, _p(self.sched.sab), _p(self.sched.omab), B, HW,
                        self.T, _p(sb.xpert), _p(sb.t_in), s)
         self.eng.repack(P, True, s)
-        eps = self.eng.forward(sb.ws, P, sb.xpert, sb.t_in, sb.c, self.sc[:nf], self.sc[nf:], B, s)
+        eps = self.eng.forward(sb.ws, P, sb.xpert, sb.t_in, c_in, self.sc[:nf], self.sc[nf:], B, s)
         gnum = float(B * HW) if self.grad_numel is None else float(self.grad_numel)
         lb.cdm_mse(_p(eps), _p(sb.noise), B * HW, gnum, _p(sb.deps), _p(self.partial), self.nb, _p(self.loss),
                    _p(self.grads["out.3.bias"]), _p(self.nonfinite), s)
@@ -216,8 +339,14 @@ class Trainer:
         self.eng.backward(sb.ws, P, sb.deps, self.grads, s, out3_bias_done=True, on_stage=hook)
         if self.ddp:
             self.bucketer.wait()
-        lb.cdm_adam(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), self.total, _p(self.opt_state),
-                    _p(self.adam_bc), self.adam_bc.shape[0], self.betas[0], self.betas[1], self.eps, 1.0 / self.world, s)
+        if self.ema is None:
+            lb.cdm_adam(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), self.total, _p(self.opt_state),
+                        _p(self.adam_bc), self.adam_bc.shape[0], self.betas[0], self.betas[1], self.eps,
+                        1.0 / self.world, s)
+        else:
+            lb.cdm_adam_ema(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), _p(self.ema), self.total,
+                            _p(self.opt_state), _p(self.adam_bc), self.adam_bc.shape[0], self.betas[0], self.betas[1],
+                            self.eps, 1.0 / self.world, _p(self.ema_decay), s)
         lb.cdm_counter_add(_p(self.ctr), 1, s)
 
     def _rank(self):
@@ -239,10 +368,13 @@ class Trainer:
         """One training step on batch (x0 [B,1,H,H] in [0,1], c [B, n_cfeat] or None = unconditional).
 
         ``inject=(noise [B,1,H,H], t [B] int, shortcut [2*n_feat] = weight|bias)`` replaces the on-device
-        Philox draws for this step (parity testing; runs eagerly).
+        Philox draws for this step (parity testing; runs eagerly).  With ``p_uncond > 0`` it may carry a 4th element,
+        ``keep [B]`` (0 / 1), in place of the context-dropout draw: rows with keep == 0 train on c = 0.
         ``global_count`` (data parallel): the number of samples all ranks process in this step when the ranks'
         batches differ in size; the gradient is then the mean over those samples (each rank weighted by its
         sample count, F.mse_loss over the union) instead of the mean of per-rank means."""
+        if self._in_ema:
+            raise RuntimeError("Trainer.step inside ema_weights(): the parameters hold the EMA")
         self._inject = inject
         B = self.B if x0 is None else x0.shape[0]
         HW = self.H * self.H
@@ -315,4 +447,6 @@ class _StepBufs:
         self.t_in = torch.empty(B, device=dev)
         self.xpert = torch.empty(B, H, H, device=dev)
         self.deps = torch.empty(B, H, H, device=dev)
+        self.c_eff = torch.zeros(B, ncf, device=dev)                 # c after context dropout (p_uncond > 0)
+        self.keep = torch.ones(B, dtype=torch.int32, device=dev)     # its mask: 0 = dropped
         self.ws = eng.workspace(B, True)

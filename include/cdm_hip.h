@@ -411,6 +411,20 @@ int cdm_counter_add(int* ctr, int delta, void* stream);
  * grad_scale multiplies g (1/world for a summed data-parallel gradient). */
 int cdm_adam(float* p, const float* g, float* m, float* v, long long n, double* state, const double* bc, int nbc,
              double beta1, double beta2, double eps, float grad_scale, void* stream);
+/* cdm_adam plus the exponential moving average of the parameters in the same pass: p, m, v and state come out
+ * bit-identical to cdm_adam; then ema[i] = fmaf(omd, p_new - ema[i], ema[i]) with omd = (float)(1 - *ema_decay)
+ * (*ema_decay == 0: ema[i] = p_new exactly).  ema_decay is a device double[1], read at run time like lr in state, so
+ * it can change between replays of a captured step.  hipErrorInvalidValue, nothing launched: nbc < 1, n < 0, ema or
+ * ema_decay null.  n == 0 advances the step count only. */
+int cdm_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state, const double* bc,
+                 int nbc, double beta1, double beta2, double eps, float grad_scale, const double* ema_decay,
+                 void* stream);
+/* context dropout (training for classifier-free guidance): u[b] = element b of what
+ * cdm_philox_uniform(out, B, 0, 1, seed, sub, sub_dev) writes; c_out[b][:] = u[b] < p_drop ? 0 : c[b][:] for c, c_out
+ * [B][ncf]; keep (optional, int [B]) = 0 where the row was dropped, else 1.  c_out must not be c.
+ * hipErrorInvalidValue: p_drop outside [0, 1] or NaN, B < 1, ncf < 1, c or c_out null, c_out == c. */
+int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsigned long long seed, unsigned int sub,
+                     const int* sub_dev, float* c_out, int* keep, void* stream);
 /* weight repacking (+ eval-mode BatchNorm folding) */
 /* kc = 0: K order tap-major (k = tap*C + ci); kc = 16: channel-chunk-major (k = ((ci/16)*9 + tap)*16 + ci%16),
  * the order cdm_conv3x3_fwd(kc = 16) consumes (wdg is chunked over Cout).  ConvTranspose packing: */
