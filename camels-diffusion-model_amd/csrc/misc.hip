@@ -986,6 +986,52 @@ __global__ void denoise_kernel(const float* xin, float* x, float* x2, long long 
     }
 }
 
+// Strided (DDIM) sampler prologue: the device counter holds the position k = S..1 in the timestep subsequence
+// steps[0..S] (steps[0] = 0, steps[S] = T):
+//   k = *ctr; *ctr = k - 1; cur_k = k; cur_i = i = steps[k]; t_cur = (float)((double)i / T); shortcut row S - k.
+// A counter outside 1..S (a replay past the last position) writes nothing.
+__global__ void sample_prologue_sub_kernel(int* ctr, int S, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
+                                           const float* sc_table, int sc_row, float* sc_cur) {
+    const int k = *ctr;
+    __syncthreads();
+    if (k < 1 || k > S) return;
+    if (threadIdx.x == 0) {
+        const int i = steps[k];
+        *ctr = k - 1; *cur_i = i; *cur_k = k; *t_cur = (float)((double)i / (double)T);
+    }
+    if (sc_table)
+        for (int q = threadIdx.x; q < sc_row; q += blockDim.x) sc_cur[q] = sc_table[(long long)(S - k) * sc_row + q];
+}
+
+// Strided update from i = steps[k] to j = steps[k-1] (generalised DDIM, noise predicted with sqrt(1 - ab) as in
+// denoise_kernel): x <- (cx[k]*x + ce[k]*eps) + sigma[k]*z ;  eps = eu + w (ec - eu) when cfg (model batch = 2n).
+// cx / ce / sigma [S+1]: host tables (diffusion.ddim_tables).  z is neither read nor drawn when sigma[k] == 0 (eta = 0,
+// and the last position); else z_table[(S-k)][e] when given, else Philox(seed, stream i) keyed by the timestep.
+// Writes x into both halves of the model-input buffer (x2 may alias x), and a snapshot when slot[k] >= 0.
+__global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
+                                 float w, const int* cur_i, const int* cur_k, const float* cx, const float* ce,
+                                 const float* sigma, int S, const float* z_table, long long zstride,
+                                 unsigned long long seed, const long long* seed_dev, const int* snap_slot, float* snaps) {
+#pragma clang fp contract(off)  // separate fp32 roundings: (cx*x + ce*ep) + sg*z as a torch CPU restatement computes it
+    const int i = *cur_i, k = *cur_k;
+    if (k < 1 || k > S) return;
+    const float a = cx[k], c = ce[k], sg = sigma[k];
+    const int slot = snap_slot ? snap_slot[k] : -1;
+    const unsigned long long sd = seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
+        float ep = eps[e];
+        if (cfg) { const float eu = eps[numel + e]; ep = eu + w * (ep - eu); }
+        float v = a * xin[e] + c * ep;
+        if (sg != 0.f) {
+            const float z = z_table ? z_table[(long long)(S - k) * zstride + e] : philox_normal(sd, (uint32_t)i, e);
+            v = v + sg * z;
+        }
+        x[e] = v;
+        if (x2) { x2[e] = v; x2[numel + e] = v; }
+        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Adam = torch.optim.Adam's single-tensor step (torch/optim/adam.py _single_tensor_adam, the path the
 // reference's CPU run takes; code/train_diffusion_condition.py:200,229), with lr / step in device memory so
@@ -1367,6 +1413,26 @@ CDM_API int cdm_denoise(const float* xin, float* x, float* x2, long long numel, 
                         float* snaps, int T, void* stream) {
     hipLaunchKernelGGL(denoise_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w, cur_i,
                        coef, sa, sb, z_table, zstride, seed, seed_dev, snap_slot, snaps, T);
+    return cdm_status();
+}
+CDM_API int cdm_sample_prologue_sub(int* ctr, int npos, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
+                                    const float* sc_table, int sc_row, float* sc_cur, void* stream) {
+    if (!ctr || !steps || !cur_i || !cur_k || !t_cur || npos < 1 || T < npos || (sc_table && (!sc_cur || sc_row < 0)))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_prologue_sub_kernel, dim3(1), dim3(256), 0, S(stream), ctr, npos, T, steps, cur_i, cur_k, t_cur,
+                       sc_table, sc_row, sc_cur);
+    return cdm_status();
+}
+CDM_API int cdm_ddim_step(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                          const int* cur_i, const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
+                          const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
+                          const int* snap_slot, float* snaps, void* stream) {
+    if (!xin || !x || !eps || !cur_i || !cur_k || !cx || !ce || !sigma || npos < 1 || numel < 0 || zstride < 0 ||
+        (snap_slot && !snaps))
+        return (int)hipErrorInvalidValue;
+    if (numel == 0) return 0;
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w,
+                       cur_i, cur_k, cx, ce, sigma, npos, z_table, zstride, seed, seed_dev, snap_slot, snaps);
     return cdm_status();
 }
 CDM_API int cdm_adam(float* p, const float* g, float* m, float* v, long long n, double* state, const double* bc,

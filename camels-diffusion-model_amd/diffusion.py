@@ -20,6 +20,11 @@ RNG modes (``z_source``):
             RNG in exactly the order the reference's *GPU* run does (its z come from the CUDA generator).
   "host":   everything from the CPU RNG in the order of the reference's *CPU* run (x_T, then per step
             z then shortcut(s)); z is pre-drawn into a device table — bit-compatible with the oracle.
+
+Strided sampling (DDIM, not in the reference): :class:`DDIMSampler` walks a subsequence of S of the T timesteps
+(:func:`timestep_subsequence`) with the generalised update of :func:`ddim_tables` (eta = 0 deterministic, eta = 1 the
+ancestral variance), on the same captured step graph; ``DDPM.sample_ddim`` / ``sample_ddim_from_noise`` and
+``sample_ddpm(..., steps=S)`` are its entry points.
 """
 from __future__ import annotations
 
@@ -146,15 +151,106 @@ def snapshot_slots(T: int, save_rate: int = 20):
     return slots, k
 
 
+def timestep_subsequence(T: int, S: Optional[int] = None, spacing="uniform"):
+    """The timesteps tau_1 < ... < tau_S = T a strided sampler visits (in reverse), as a list of ints.
+
+    ``spacing``: ``"uniform"``: tau_k = round(k T / S) (halves round up); ``"quadratic"``: tau_k = max(ceil(T (k/S)^2), k)
+    (denser near t = 0); or an explicit increasing sequence of ints (``S`` is then None or its length).  Pure host
+    function.  Raises ValueError unless 1 <= tau_1, the sequence is strictly increasing and tau_S == T; nothing is
+    repaired."""
+    T = int(T)
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    if isinstance(spacing, str):
+        if S is None or int(S) != S or int(S) < 1:
+            raise ValueError(f"steps must be a positive integer, got {S!r}")
+        S = int(S)
+        if S > T:
+            raise ValueError(f"steps = {S} exceeds the {T} timesteps of the schedule")
+        if spacing == "uniform":
+            tau = [(2 * k * T + S) // (2 * S) for k in range(1, S + 1)]          # exact integer round-half-up
+        elif spacing == "quadratic":
+            tau = [max(-((-T * k * k) // (S * S)), k) for k in range(1, S + 1)]    # exact integer ceil
+        else:
+            raise ValueError(f"spacing must be 'uniform', 'quadratic' or a list of timesteps, got {spacing!r}")
+    else:
+        raw = [v.item() if hasattr(v, "item") else v for v in spacing]
+        if any(isinstance(v, bool) or int(v) != v for v in raw):
+            raise ValueError("an explicit timestep list must hold integers")
+        tau = [int(v) for v in raw]
+        if S is not None and int(S) != len(tau):
+            raise ValueError(f"steps = {S} but the explicit timestep list has {len(tau)} entries")
+    if not tau:
+        raise ValueError("the timestep list is empty")
+    if tau[0] < 1:
+        raise ValueError(f"the first timestep must be >= 1, got {tau[0]}")
+    if any(b <= a for a, b in zip(tau, tau[1:])):
+        raise ValueError("the timesteps must be strictly increasing")
+    if tau[-1] != T:
+        raise ValueError(f"the last timestep must be T = {T}, got {tau[-1]}")
+    return tau
+
+
+def ddim_tables(ab_t, taus, eta: float = 0.0):
+    """Coefficient tables (cx, ce, sigma) of the strided update, fp32 numpy arrays of S + 1 entries indexed by the
+    position k = 1..S (entry 0 is the unused identity 1, 0, 0).
+
+    With tau_0 = 0 (ab_0 = 1), a step from i = tau_k to j = tau_{k-1} is
+
+        sigma = eta sqrt((1 - ab_j) / (1 - ab_i)) sqrt(1 - ab_i / ab_j)
+        cx    = sqrt(ab_j / ab_i)
+        ce    = sqrt(1 - ab_j - sigma^2) - sqrt(ab_j (1 - ab_i) / ab_i)
+        x_j   = cx x_i + ce eps + sigma z                 (sigma = 0, no z, when j = 0)
+
+    This is DDIM (Song et al. 2021, eq. 12) in the convention of the reference's *sampler*, whose denoise_add_noise
+    (code/train_diffusion_condition.py:274-279) treats the network output as the noise of x = sqrt(ab) x0 +
+    sqrt(1 - ab) eps: over the full sequence 1..T with eta = 1 the tables are that function's 1 / sqrt(a),
+    -(1 - a) / (sqrt(1 - ab) sqrt(a)) and the posterior variance b (1 - ab_{t-1}) / (1 - ab_t).  It does not follow
+    the (1 - ab) noise factor of perturb_input (:202-203), which the reference's own sampler ignores too.
+
+    ``ab_t`` is the fp32 table of the Schedule (T + 1 entries); the arithmetic is fp64 numpy, rounded once to fp32, so
+    the tables do not depend on the host's vectorised fp32 sqrt (the concern of :func:`sqrt_scalar_f32`).  Pure host
+    function."""
+    if torch.is_tensor(ab_t):
+        ab_t = ab_t.detach().cpu().numpy()
+    ab = np.asarray(ab_t, dtype=np.float32).astype(np.float64).reshape(-1)
+    eta = float(eta)
+    if not (eta >= 0.0) or not np.isfinite(eta):
+        raise ValueError(f"eta must be finite and >= 0, got {eta}")
+    tau = timestep_subsequence(ab.size - 1, None, taus)
+    S = len(tau)
+    i = np.array(tau, dtype=np.int64)
+    j = np.array([0] + tau[:-1], dtype=np.int64)
+    ab_i, ab_j = ab[i], ab[j]
+    ab_j[0] = 1.0                                             # tau_0 = 0: ab_0 = 1 by definition
+    with np.errstate(divide="ignore", invalid="ignore"):     # a degenerate schedule is reported below
+        sigma = eta * np.sqrt((1 - ab_j) / (1 - ab_i)) * np.sqrt(1 - ab_i / ab_j)
+        sigma[0] = 0.0
+        rad = 1 - ab_j - sigma * sigma
+        if (rad < 0).any():
+            raise ValueError(f"eta = {eta} makes sigma^2 exceed 1 - ab_j at position {int(np.argmax(rad < 0)) + 1}")
+        cx = np.sqrt(ab_j / ab_i)
+        ce = np.sqrt(rad) - np.sqrt(ab_j * (1 - ab_i) / ab_i)
+    out = []
+    for v, v0 in ((cx, 1.0), (ce, 0.0), (sigma, 0.0)):
+        if not np.isfinite(v).all():
+            raise ValueError("the schedule gives non-finite DDIM coefficients (ab_t must lie in (0, 1) for t >= 1)")
+        out.append(np.concatenate([[v0], v]).astype(np.float32))
+    assert all(o.size == S + 1 for o in out)
+    return tuple(out)
+
+
 class GraphSampler:
     """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  save_rate: int = 20, z_source: str = "device", steps_per_graph: int = 10, seed: int = 1234,
-                 snapshots: bool = True, use_graph: bool = True):
+                 snapshots: bool = True, use_graph: bool = True, positions: Optional[int] = None):
+        """``positions``: the number of steps of a run when it is not T (DDIMSampler); it sizes the per-step tables."""
         from .model import ContextUnet  # noqa: F401
         self.model, self.sched, self.n = model, sched, n
         self.T = sched.T
+        self.npos = self.T if positions is None else int(positions)
         self.guide_w = float(guide_w)
         self.cfg = self.guide_w > 0 and params is not None
         self.z_source = z_source
@@ -181,17 +277,20 @@ class GraphSampler:
         self.cur_i = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int32, device=dev)
         self.row = 2 * self.sets * nf
-        self.sc_table = E(self.T, self.row)
+        self.sc_table = E(self.npos, self.row)
         self.sc_cur = E(self.row)
-        slots, nslots = snapshot_slots(self.T, save_rate)
+        slots, nslots = snapshot_slots(self.npos, save_rate)
         self.nslots = nslots if snapshots else 0
         self.slot = torch.from_numpy(slots).to(dev) if snapshots else None
         self.snaps = E(max(self.nslots, 1), n * H * H)
-        self.z_table = E(max(self.T - 1, 1), n * H * H) if z_source == "host" else None
+        self.z_table = E(max(self.npos - 1, 1), n * H * H) if self._needs_z_table() else None
         self.zseed = torch.zeros(1, dtype=torch.int64, device=dev)    # per-run Philox key (device z mode)
         self.K = max(1, int(steps_per_graph))
         self.use_graph = use_graph
         self.graph = None
+
+    def _needs_z_table(self):
+        return self.z_source == "host"
 
     # RNG draws in the reference order ------------------------------------------------------------
     def _draw_shortcut_row(self):
@@ -235,7 +334,7 @@ class GraphSampler:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             # warm-up launch of every kernel before capture (code objects resident)
-            self.ctr.fill_(self.T)
+            self.ctr.fill_(self.npos)
             self._step(s.cuda_stream)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
@@ -250,11 +349,11 @@ class GraphSampler:
         if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
             self.P, self.graph = P, None                    # parameters were re-homed: re-capture
         eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
-        if self.use_graph and self.graph is None and self.T >= self.K:
+        if self.use_graph and self.graph is None and self.npos >= self.K:
             self._capture()
 
     def run(self, x_T: torch.Tensor, steps: Optional[int] = None):
-        """Run T steps (or the first ``steps``) from x_T [n,1,H,H].
+        """Run every step (T of them; S for the strided sampler), or the first ``steps``, from x_T [n,1,H,H].
 
         Returns (x [n,1,H,H], intermediate np [slots,n,1,H,H] or None)."""
         n, H = self.n, self.H
@@ -264,11 +363,11 @@ class GraphSampler:
             # Drawn before prepare(): a graph capture moves the generator's offset.
             self.zseed.random_()
         self.prepare()
-        total = self.T if steps is None else min(int(steps), self.T)
+        total = self.npos if steps is None else min(int(steps), self.npos)
         self.xbuf[:n] = x_T.to(self.dev, torch.float32).reshape(n, H, H)
         if self.cfg:
             self.xbuf[n:] = self.xbuf[:n]
-        self.ctr.fill_(self.T)
+        self.ctr.fill_(self.npos)
         done = 0
         if self.graph is not None:
             while done + self.K <= total:
@@ -283,6 +382,61 @@ class GraphSampler:
         if self.nslots:
             inter = self.snaps[: self.nslots].reshape(self.nslots, n, 1, H, H).cpu().numpy()
         return x, inter
+
+
+class DDIMSampler(GraphSampler):
+    """Strided reverse diffusion: S of the T timesteps (:func:`timestep_subsequence`) with the update of
+    :func:`ddim_tables`, on GraphSampler's buffers, RNG modes, snapshots and captured step graph.
+
+    The device counter holds the position p = S..1; ``cdm_sample_prologue_sub`` turns it into the timestep
+    tau_p the network sees, and ``cdm_ddim_step`` applies x <- (cx[p] x + ce[p] eps) + sigma[p] z.  Snapshots follow
+    the reference's rule on positions: ``snapshot_slots(S, save_rate)``.  CPU-RNG order (z_source="host"), for
+    p = S..1: z (only when eta > 0 and p > 1), then the shortcut row(s), cond before uncond; eta = 0 draws no z at all.
+    In "device" mode z is Philox stream tau_p of the per-run key, as the full sampler's stream i."""
+
+    def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
+                 steps=50, eta: float = 0.0, spacing="uniform", save_rate: int = 20, z_source: str = "device",
+                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True):
+        self.taus = timestep_subsequence(sched.T, steps, spacing)
+        self.S = len(self.taus)
+        self.eta = float(eta)
+        cx, ce, sg = ddim_tables(sched.ab_t, self.taus, self.eta)          # validates eta before anything is allocated
+        super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, positions=self.S)
+        dev = self.dev
+        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
+        self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(dev) for v in (cx, ce, sg))
+        self.cur_k = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _needs_z_table(self):
+        return self.z_source == "host" and self.eta > 0 and self.S > 1
+
+    def prepare_rng(self, host_z: bool):
+        n, H = self.n, self.H
+        rows, zs = [], []
+        for p in range(self.S, 0, -1):
+            if host_z and self.eta > 0 and p > 1:
+                zs.append(torch.randn(n, 1, H, H))
+            rows.append(self._draw_shortcut_row())
+        self.sc_table.copy_(torch.stack(rows))
+        if zs:
+            if self.z_table is None:
+                raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
+            self.z_table.copy_(torch.stack(zs).reshape(self.S - 1, n * H * H))
+
+    def _step(self, s):
+        lb = lib()
+        nf, n = self.model.n_feat, self.n
+        lb.cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
+                                   _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+        half = self.sets * nf
+        sc_w, sc_b = self.sc_cur[:half], self.sc_cur[half:]
+        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, sc_w, sc_b, n, s)
+        numel = n * self.H * self.H
+        lb.cdm_ddim_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                         1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.cur_k), _p(self.cx), _p(self.ce),
+                         _p(self.sigma), self.S, _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
+                         _p(self.snaps), s)
 
 
 class DDPM:
@@ -306,10 +460,17 @@ class DDPM:
     def denoise_add_noise(self, x, t, pred_noise, z=None):
         return denoise_add_noise(x, t, pred_noise, z, self.sched)
 
-    def _sampler(self, n, guide_w, params, save_rate):
+    def _sampler(self, n, guide_w, params, save_rate, ddim=None):
+        """The cached sampler of a configuration; ``ddim = (steps, eta, spacing)`` selects the strided one."""
         key = (n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, self.z_source)
+        if ddim is not None:
+            steps, eta, spacing = ddim
+            key += (steps, float(eta), spacing if isinstance(spacing, str) else tuple(spacing))
         smp = self._samplers.get(key)
-        if smp is None:
+        if smp is None and ddim is not None:
+            smp = self._samplers[key] = DDIMSampler(self.model, self.sched, n, guide_w, params, steps, eta, spacing,
+                                                    save_rate, self.z_source, seed=self.seed)
+        elif smp is None:
             smp = self._samplers[key] = GraphSampler(self.model, self.sched, n, guide_w, params, save_rate,
                                                      self.z_source, seed=self.seed)
         elif params is not None:
@@ -337,16 +498,45 @@ class DDPM:
         return smp.run(noise_images)
 
 
+    @torch.no_grad()
+    def sample_ddim(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=50, eta=0.0,
+                    spacing="uniform", save_rate=20):
+        """sample_ddpm on ``steps`` of the T timesteps (:class:`DDIMSampler`; ``spacing``: "uniform", "quadratic" or an
+        explicit increasing timestep list ending at T, then ``steps`` may be None) -> (samples, intermediate).  x_T and
+        random params consume the CPU RNG as sample_ddpm does; eta = 0 is deterministic given x_T and the shortcut
+        draws, eta = 1 has the ancestral sampler's variance.  Snapshots: snapshot_slots(steps, save_rate) on positions."""
+        assert size == self.model.h
+        x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
+        if params is None:
+            params = torch.rand(n_sample, self.n_cfeat)
+        smp = self._sampler(n_sample, guide_w, params, save_rate, (steps, eta, spacing))
+        smp.prepare_rng(host_z=self.z_source == "host")
+        return smp.run(x_T)
+
+    @torch.no_grad()
+    def sample_ddim_from_noise(self, noise_images, params=None, steps=50, eta=0.0, spacing="uniform", save_rate=20,
+                               guide_w=0.0):
+        """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_ddim`)."""
+        n = noise_images.shape[0]
+        smp = self._sampler(n, guide_w, params, save_rate, (steps, eta, spacing))
+        smp.prepare_rng(host_z=self.z_source == "host")
+        return smp.run(noise_images)
+
+
 @torch.no_grad()
 def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.0, timesteps=1000, b_t=None,
-                a_t=None, ab_t=None, z_source="device"):
+                a_t=None, ab_t=None, z_source="device", *, steps=None, eta=0.0, spacing="uniform"):
     """Functional sampler of code/sample_power_spectra.py:71-110 (returns the final x only).  b_t / a_t / ab_t are
-    the caller's schedule, as in the reference (all three or none: None builds the default schedule)."""
+    the caller's schedule, as in the reference (all three or none: None builds the default schedule).
+    ``steps`` (keyword only; None: the reference's T-step ancestral sampler) runs DDPM.sample_ddim with ``eta`` and
+    ``spacing`` on that many of the timesteps."""
     given = [v is not None for v in (b_t, a_t, ab_t)]
     if any(given) and not all(given):
         raise ValueError("pass all of b_t, a_t, ab_t or none of them")
     d = DDPM(model, timesteps, device or model.out[3].weight.device, z_source=z_source,
              sched_tensors=(b_t, a_t, ab_t) if all(given) else None)
+    if steps is not None:
+        return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing)[0]
     if params is None:
         x_T = torch.randn(n_sample, 1, size, size)
         params = torch.rand(n_sample, 6 if model.n_cfeat == 6 else model.n_cfeat)

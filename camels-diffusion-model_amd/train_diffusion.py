@@ -30,6 +30,9 @@ Training for guided sampling (all off by default; without them the outputs are t
                  c = 0 forward of classifier-free guidance (--guide-w > 0) is one the model was trained on.
   --ema DECAY    keep an exponential moving average of the parameters; the sampling at the end runs on it, and every
                  model_epoch_N.pth gets a model_epoch_N_ema.pth beside it.
+  --sample-steps S [--eta E] [--spacing uniform|quadratic]
+                 run the sampling at the end on S of the TIMESTEPS with the strided DDIM sampler (eta 0: deterministic)
+                 instead of all of them; the log lines then name steps=S, eta=E.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -72,7 +75,14 @@ def main(argv=None):
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep and sample from EMA weights")
     ap.add_argument("--resume", default=None, metavar="PATH",
                     help="write trainer_epoch_N.pt checkpoints; continue from PATH if it exists")
+    ap.add_argument("--sample-steps", type=int, default=0, metavar="S",
+                    help="sample on S of the TIMESTEPS (strided DDIM sampler); 0: the reference's ancestral sampler")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0 deterministic, 1 ancestral variance)")
+    ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform",
+                    help="how --sample-steps picks its timesteps")
     a = ap.parse_args(argv)
+    if a.sample_steps < 0 or a.sample_steps > a.timesteps:
+        ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -216,23 +226,31 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
     noise = torch.randn(x.shape, device=dev)
     x_T = cdm_amd.perturb_input(x, a.timesteps, noise, d.sched)
     t0 = time.time()
-    rec, inter = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w)
+    ddim = dict(steps=a.sample_steps, eta=a.eta, spacing=a.spacing) if a.sample_steps > 0 else None
+    how = f"T={a.timesteps}" + (f", steps={a.sample_steps}, eta={a.eta:g}" if ddim else "")
+    if ddim:
+        rec, inter = d.sample_ddim_from_noise(x_T, p, guide_w=a.guide_w, **ddim)
+    else:
+        rec, inter = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w)
     torch.cuda.synchronize()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, "reconstructed_images.npy"), rec.cpu().numpy())
     np.save(os.path.join(out_dir, "intermediate.npy"), inter)
-    log.write(f"Reconstruction of {ns} maps, T={a.timesteps}: {dt:.2f} s\n")
+    log.write(f"Reconstruction of {ns} maps, {how}: {dt:.2f} s\n")
     # the reference's post-sampling statistics (code/train_diffusion.py:250, diffusion_utilities.py:370),
     # on the HIP statistics kernels; the plotted arrays go to .npz files
     cdm_amd.compare_distributions(x[:, 0].cpu().numpy(), rec[:, 0].cpu().numpy(), out_dir)
     cdm_amd.compare_power_spectra(x, rec, out_dir)
     if conditional:
         t0 = time.time()
-        samples, _ = d.sample_ddpm(ns, H, dev, p, a.guide_w)
+        if ddim:
+            samples, _ = d.sample_ddim(ns, H, dev, p, a.guide_w, **ddim)
+        else:
+            samples, _ = d.sample_ddpm(ns, H, dev, p, a.guide_w)
         torch.cuda.synchronize()
         dt = time.time() - t0
         np.save(os.path.join(out_dir, "generated_samples.npy"), samples.cpu().numpy())
-        log.write(f"Sampling {ns} maps (w={a.guide_w}), T={a.timesteps}: {dt:.2f} s ({ns / dt:.3f} img/s)\n")
+        log.write(f"Sampling {ns} maps (w={a.guide_w}), {how}: {dt:.2f} s ({ns / dt:.3f} img/s)\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

@@ -395,6 +395,21 @@ int cdm_denoise(const float* xin, float* x, float* x2, long long numel, const fl
                 const int* cur_i, const float* coef, const float* sa, const float* sb, const float* z_table,
                 long long zstride, unsigned long long seed, const long long* seed_dev, const int* snap_slot,
                 float* snaps, int T, void* stream);
+/* strided (DDIM) sampler over the timestep subsequence steps[0..npos] (steps[0] = 0 < steps[1] < ... < steps[npos] = T;
+ * the device counter holds the position k = npos..1).  Prologue: cur_k = k, cur_i = i = steps[k],
+ * t_cur = (float)((double)i / T), *ctr = k - 1, shortcut row npos - k of sc_table.  A counter outside 1..npos writes
+ * nothing (and the step kernel then does nothing either). */
+int cdm_sample_prologue_sub(int* ctr, int npos, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
+                            const float* sc_table, int sc_row, float* sc_cur, void* stream);
+/* x <- (cx[k] x + ce[k] eps) + sigma[k] z with separate fp32 roundings; eps = eu + w (ec - eu) when cfg.  cx / ce /
+ * sigma [npos + 1] are host-built tables indexed by the position k = *cur_k.  sigma[k] == 0: z is neither read nor
+ * drawn; else z = z_table[(npos - k) * zstride + e] when given, else Philox keyed by seed ^ *seed_dev, stream
+ * i = *cur_i (the timestep, as cdm_denoise).  Writes x (and both halves of x2 when given; x2 may alias x), and the
+ * snapshot slot snap_slot[k] (snap_slot [npos + 1], optional) of snaps when >= 0. */
+int cdm_ddim_step(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                  const int* cur_i, const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
+                  const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
+                  const int* snap_slot, float* snaps, void* stream);
 /* randn_like / randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
