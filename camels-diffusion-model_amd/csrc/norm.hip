@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(F f, int HWp, int C, i
 
 template <class F>
 static int launch_reduce(const F& f, int N, int HWp, int C, int csize, float* slab, hipStream_t s) {
-    if (C % 4 || C > 1024) return (int)hipErrorInvalidValue;
+    if (C < 4 || C % 4 || C > 1024) return (int)hipErrorInvalidValue;   // C < 4: the lane split 256 / (C / 4)
     const int nchunks = (HWp + csize - 1) / csize;
     hipLaunchKernelGGL(chan_reduce_kernel<F>, dim3(nchunks, N), dim3(256), 0, s, f, HWp, C, csize, slab);
     return cdm_status();
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void slab_colsum_kernel(const float* __restric
 // Block = 16 channels x 16 lanes over the S partials (strided), folded through LDS in a fixed order.
 __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const double* part, int S, int R, int C, double count,
                                        const float* gamma, const float* beta, float* rmean, float* rvar,
-                                       long long* nbt, float momentum, float eps, float* mean, float* invstd,
+                                       long long* nbt, double momentum, float eps, float* mean, float* invstd,
                                        float* scale, float* shift, const int* ymm, int ymm_ld, float* amax_z) {
     __shared__ double rs[16][17], rq[16][17];
     const int cl = threadIdx.x & 15, ln = threadIdx.x >> 4;
@@ -235,8 +235,9 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const double* part
     }
     if (rmean) {
         const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-        rmean[c] = (float)((double)momentum * mu + (1.0 - (double)momentum) * (double)rmean[c]);
-        rvar[c] = (float)((double)momentum * unb + (1.0 - (double)momentum) * (double)rvar[c]);
+        // momentum is a double: as a float, 0.1 is off by 1.5e-8 relative, more than an ulp of a cancelling update
+        rmean[c] = (float)(momentum * mu + (1.0 - momentum) * (double)rmean[c]);
+        rvar[c] = (float)(momentum * unb + (1.0 - momentum) * (double)rvar[c]);
     }
 }
 
@@ -706,7 +707,7 @@ __global__ __launch_bounds__(256) void stats_mm_kernel(const float* __restrict__
 
 CDM_API int cdm_reduce_stats_mm(const float* y, int ldy, int N, int HW, int C, int csize, float* slab, int* ymm,
                                 int ymm_ld, void* stream) {
-    if (C % 4 || C > 1024) return (int)hipErrorInvalidValue;
+    if (C < 4 || C % 4 || C > 1024) return (int)hipErrorInvalidValue;   // as launch_reduce
     const int nchunks = (HW + csize - 1) / csize;
     hipLaunchKernelGGL(stats_mm_kernel, dim3((nchunks + U0S_CG - 1) / U0S_CG, N), dim3(256), 0, S(stream), y, ldy, HW,
                        C, csize, nchunks, slab, ymm, ymm_ld);
@@ -740,7 +741,7 @@ CDM_API int cdm_slab_colsum(const float* slab, int ntiles, int R, int C, double*
 }
 
 CDM_API int cdm_bn_fwd_finalize(const double* part, int nparts, int R, int C, double count, const float* gamma,
-                                const float* beta, float* rmean, float* rvar, long long* nbt, float momentum, float eps,
+                                const float* beta, float* rmean, float* rvar, long long* nbt, double momentum, float eps,
                                 float* mean, float* invstd, float* scale, float* shift, const int* ymm, int ymm_ld,
                                 float* amax_z, void* stream) {
     if (ymm && !amax_z) return (int)hipErrorInvalidValue;
@@ -821,6 +822,8 @@ CDM_API int cdm_col_sum(const float* in, int N, int C, float* out, int accumulat
 }
 CDM_API int cdm_col_sum3(const float* in0, float* out0, const float* in1, float* out1, const float* in2, float* out2,
                          int N, int C, void* stream) {
+    // the pairs are a prefix (pair 2 needs pair 1: the kernel's blockIdx.y walks 0..k-1), each input with its output
+    if (!in0 || !out0 || (in2 && !in1) || (in1 && !out1) || (in2 && !out2)) return (int)hipErrorInvalidValue;
     const int k = in2 ? 3 : (in1 ? 2 : 1);
     ColSum3 cs{{in0, in1, in2}, {out0, out1, out2}};
     hipLaunchKernelGGL(col_sum_kernel, dim3((C + 63) / 64, k), dim3(256), 0, S(stream), cs, N, C, 0);

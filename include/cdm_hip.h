@@ -244,7 +244,9 @@ int cdm_slab_reduce(const float* slab, int splits, int M, int N, float* out, lon
                     long long s_lo, int csplit, int accumulate, float scale, void* stream);
 
 /* ---- normalisation / pooling / FiLM (csrc/norm.hip) ------------------------------------------- */
-/* per-(image, pixel-chunk) partial sums (slab[N][chunks][R][C]) */
+/* per-(image, pixel-chunk) partial sums (slab[N][chunks][R][C]).  The chunked reducers (cdm_reduce_stats, _stats_mm,
+ * _sum, cdm_norm_bwd_reduce) take 4 <= C <= 1024, C % 4 == 0; any other C returns hipErrorInvalidValue before a
+ * launch (C = 0 would divide by zero in the lane split 256 / (C / 4)) and writes nothing. */
 int cdm_reduce_stats(const float* y, int ldy, int N, int HW, int C, int csize, float* slab, void* stream);
 /* cdm_reduce_stats (identical slab) + optional (ymm != NULL) per-channel max / min of y as ordered-int keys, atomic max
  * into ymm[c] / min into ymm[ymm_ld + c] (cleared by the caller to INT_MIN / INT_MAX): the C_in = 1 init conv's
@@ -258,9 +260,10 @@ int cdm_norm_bwd_reduce(int mode, const float* g, int ldg, const float* y, int l
                         int cpg, const float* film_a, int film_an, int csize, float* slab, void* stream);
 /* stage 1 of every slab fold: part[s][r][c] = sum_{tiles of split s} slab[t][r][c] in fp64 (parallel) */
 int cdm_slab_colsum(const float* slab, int ntiles, int R, int C, double* part, int splits, void* stream);
-/* BatchNorm2d train statistics + running-stat update (diffusion_utilities.py:28,35; momentum 0.1, eps 1e-5) */
+/* BatchNorm2d train statistics + running-stat update (diffusion_utilities.py:28,35; momentum 0.1, eps 1e-5).  momentum
+ * is a double (torch's own scalar type): the update is formed in fp64 and rounded once. */
 int cdm_bn_fwd_finalize(const double* part, int nparts, int R, int C, double count, const float* gamma,
-                        const float* beta, float* rmean, float* rvar, long long* nbt, float momentum, float eps,
+                        const float* beta, float* rmean, float* rvar, long long* nbt, double momentum, float eps,
                         float* mean, float* invstd, float* scale, float* shift, const int* ymm, int ymm_ld,
                         float* amax_z, void* stream);
 /* (ymm optional: the per-channel max / min keys of the layer's y from cdm_conv3x3_fwd_h3_ex; amax_z then receives
@@ -291,7 +294,9 @@ int cdm_gn_bwd_finalize(const float* slab, int N, int nchunks, int C, int G, dou
                         float* pdbias, void* stream);
 int cdm_slab_sum_nc(const float* slab, int N, int nchunks, int R, int r, int C, float* out, void* stream);
 int cdm_col_sum(const float* in, int N, int C, float* out, int accumulate, void* stream);
-/* up to three column sums out_k[c] = sum_n in_k[n][c] in one launch (in1 / in2 may be null) */
+/* up to three column sums out_k[c] = sum_n in_k[n][c] in one launch.  in1 / in2 may be null, as a suffix: one pair
+ * (in1 = in2 = NULL), two (in2 = NULL) or three.  in2 without in1, or any given input without its output, returns
+ * hipErrorInvalidValue before a launch. */
 int cdm_col_sum3(const float* in0, float* out0, const float* in1, float* out1, const float* in2, float* out2, int N,
                  int C, void* stream);
 /* out = [MaxPool2d(2)]([cemb*](ReLU(y*s+t))[+temb])[+ 1x1 shortcut(x)]  — flags 1 pool, 2 FiLM, 4 resid, 8 relu
