@@ -1032,8 +1032,38 @@ __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long lon
     }
 }
 
+// Second-order multistep update (DPM-Solver++ 2M) from i = steps[k] to j = steps[k-1], on the data prediction:
+//   d = (x - sq[k]*eps) * ra[k];  D = d when c1[k] == 0, else c0[k]*d + c1[k]*dprev;  x <- cx[k]*x + cd[k]*D;  dprev <- d
+// eps = eu + w (ec - eu) when cfg (model batch = 2n).  sq / ra / c0 / c1 / cx / cd [S+1]: host tables
+// (diffusion.dpmpp_tables).  dprev is not read where c1[k] == 0 (the first position, where it is uninitialised or stale
+// from an earlier run, the last, and every position at order 1): 0 * NaN must not reach x.  No z: the solver is
+// deterministic.  Writes x into both halves of the model-input buffer (x2 may alias x), and a snapshot when slot[k] >= 0.
+__global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
+                                  float w, const int* cur_k, const float* sq, const float* ra, const float* c0,
+                                  const float* c1, const float* cx, const float* cd, int S, float* dprev,
+                                  const int* snap_slot, float* snaps) {
+#pragma clang fp contract(off)  // separate fp32 roundings, in the order a torch CPU restatement computes them
+    const int k = *cur_k;
+    if (k < 1 || k > S) return;
+    const float s = sq[k], r = ra[k], a0 = c0[k], a1 = c1[k], a = cx[k], c = cd[k];
+    const int slot = snap_slot ? snap_slot[k] : -1;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
+        float ep = eps[e];
+        if (cfg) { const float eu = eps[numel + e]; ep = eu + w * (ep - eu); }
+        const float xe = xin[e];
+        const float d = (xe - s * ep) * r;
+        float D = d;
+        if (a1 != 0.f) D = a0 * d + a1 * dprev[e];
+        const float v = a * xe + c * D;
+        dprev[e] = d;
+        x[e] = v;
+        if (x2) { x2[e] = v; x2[numel + e] = v; }
+        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
-// Adam = torch.optim.Adam's single-tensor step (torch/optim/adam.py _single_tensor_adam, the path the
+// Adam =torch.optim.Adam's single-tensor step (torch/optim/adam.py _single_tensor_adam, the path the
 // reference's CPU run takes; code/train_diffusion_condition.py:200,229), with lr / step in device memory so
 // a captured step replays.
 // state (double[4]): [0] lr (a Python float, as torch keeps it), [1] step count, [2] -step_size rounded to
@@ -1433,6 +1463,18 @@ CDM_API int cdm_ddim_step(const float* xin, float* x, float* x2, long long numel
     if (numel == 0) return 0;
     hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w,
                        cur_i, cur_k, cx, ce, sigma, npos, z_table, zstride, seed, seed_dev, snap_slot, snaps);
+    return cdm_status();
+}
+CDM_API int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                           const int* cur_k, const float* sq, const float* ra, const float* c0, const float* c1,
+                           const float* cx, const float* cd, int npos, float* dprev, const int* snap_slot, float* snaps,
+                           void* stream) {
+    if (!xin || !x || !eps || !cur_k || !sq || !ra || !c0 || !c1 || !cx || !cd || !dprev || npos < 1 || numel < 0 ||
+        (snap_slot && !snaps))
+        return (int)hipErrorInvalidValue;
+    if (numel == 0) return 0;
+    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w,
+                       cur_k, sq, ra, c0, c1, cx, cd, npos, dprev, snap_slot, snaps);
     return cdm_status();
 }
 CDM_API int cdm_adam(float* p, const float* g, float* m, float* v, long long n, double* state, const double* bc,

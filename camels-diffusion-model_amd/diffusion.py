@@ -24,7 +24,10 @@ RNG modes (``z_source``):
 Strided sampling (DDIM, not in the reference): :class:`DDIMSampler` walks a subsequence of S of the T timesteps
 (:func:`timestep_subsequence`) with the generalised update of :func:`ddim_tables` (eta = 0 deterministic, eta = 1 the
 ancestral variance), on the same captured step graph; ``DDPM.sample_ddim`` / ``sample_ddim_from_noise`` and
-``sample_ddpm(..., steps=S)`` are its entry points.
+``sample_ddpm(..., steps=S)`` are its entry points.  :class:`DPMSolverSampler` walks the same subsequence with the
+second-order multistep update of :func:`dpmpp_tables` (DPM-Solver++ 2M: the previous step's data prediction is reused,
+no extra network evaluation); ``DDPM.sample_dpm`` / ``sample_dpm_from_noise`` and ``sample_ddpm(..., steps=S,
+solver="dpmpp")``.
 """
 from __future__ import annotations
 
@@ -240,6 +243,61 @@ def ddim_tables(ab_t, taus, eta: float = 0.0):
     return tuple(out)
 
 
+def dpmpp_tables(ab_t, taus, order: int = 2, dtype=np.float32):
+    """Coefficient tables (sq, ra, c0, c1, cx, cd) of the multistep update DPM-Solver++(2M) (Lu et al. 2022, algorithm
+    2), numpy arrays of S + 1 entries indexed by the position k = 1..S (entry 0 is the unused 0, 1, 1, 0, 1, 0).
+
+    With tau_0 = 0 (ab_0 = 1), alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = log(alpha / sigma), a step from
+    i = tau_k to j = tau_{k-1} with h_k = lambda_j - lambda_i (h_1 = +inf) is
+
+        sq = sigma_i,  ra = 1 / alpha_i                  d   = (x_i - sq eps) ra            (data prediction)
+        c0 = 1 + 1 / (2 r),  c1 = -1 / (2 r)             D   = c0 d + c1 d_prev             (r = h_{k+1} / h_k)
+        cx = sigma_j / sigma_i                           x_j = cx x_i + cd D ;  d_prev <- d
+        cd = alpha_j - sigma_j alpha_i / sigma_i         (= alpha_j (1 - e^{-h_k});  cx[1] = 0, cd[1] = 1)
+
+    The first position (k = S, no d_prev yet) and the last (k = 1, the step to t = 0) are first order, c0 = 1 and
+    c1 = 0, and so is every position with ``order=1``; c1 == 0 means D = d and d_prev is not read.  S <= 2 is therefore
+    first order throughout.  The first-order update is DDIM at eta = 0: cx + cd ra and -cd ra sq are ddim_tables' cx
+    and ce.  The noise convention is the sampler's, sqrt(1 - ab), as :func:`ddim_tables` documents.
+
+    ``ab_t`` is the fp32 table of the Schedule (T + 1 entries); the arithmetic is fp64 numpy, rounded once to ``dtype``
+    (np.float32 for the kernel; np.float64 returns the unrounded values).  Pure host function.  Raises ValueError for an
+    order other than 1 or 2 and for a schedule that gives non-finite coefficients or a non-increasing lambda."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order!r}")
+    if torch.is_tensor(ab_t):
+        ab_t = ab_t.detach().cpu().numpy()
+    ab = np.asarray(ab_t, dtype=np.float32).astype(np.float64).reshape(-1)
+    tau = timestep_subsequence(ab.size - 1, None, taus)
+    S = len(tau)
+    i = np.array(tau, dtype=np.int64)
+    j = np.array([0] + tau[:-1], dtype=np.int64)
+    ab_i, ab_j = ab[i], ab[j]
+    ab_j[0] = 1.0                                             # tau_0 = 0: ab_0 = 1 by definition
+    bad = ValueError("the schedule gives non-finite DPM-Solver++ coefficients (ab_t must lie in (0, 1) for t >= 1 and "
+                     "decrease along the timesteps)")
+    with np.errstate(divide="ignore", invalid="ignore"):     # a degenerate schedule is reported below
+        al_i, al_j = np.sqrt(ab_i), np.sqrt(ab_j)
+        sg_i, sg_j = np.sqrt(1 - ab_i), np.sqrt(1 - ab_j)
+        sq, ra = sg_i, 1 / al_i
+        cx = sg_j / sg_i
+        cd = al_j - sg_j * al_i / sg_i
+        h = np.log(al_j / sg_j) - np.log(al_i / sg_i)        # h[0] = h_1 = +inf (sigma_j = 0)
+        c0, c1 = np.ones(S), np.zeros(S)
+        if order == 2 and S > 2:
+            r = h[2:] / h[1:-1]                               # positions k = 2..S-1: h_{k+1} / h_k
+            c0[1:-1], c1[1:-1] = 1 + 1 / (2 * r), -1 / (2 * r)
+    if not (h[1:] > 0).all() or not h[0] > 0:
+        raise bad
+    out = []
+    for v, v0 in ((sq, 0.0), (ra, 1.0), (c0, 1.0), (c1, 0.0), (cx, 1.0), (cd, 0.0)):
+        if not np.isfinite(v).all():
+            raise bad
+        out.append(np.concatenate([[v0], v]).astype(dtype))
+    assert all(o.size == S + 1 for o in out)
+    return tuple(out)
+
+
 class GraphSampler:
     """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed."""
 
@@ -439,6 +497,51 @@ class DDIMSampler(GraphSampler):
                          _p(self.snaps), s)
 
 
+class DPMSolverSampler(GraphSampler):
+    """Strided reverse diffusion with the multistep update of :func:`dpmpp_tables` (DPM-Solver++ 2M; ``order=1`` is DDIM
+    at eta = 0 written on the data prediction), on GraphSampler's buffers, snapshots and captured step graph.
+
+    As in DDIMSampler the device counter holds the position p = S..1 and ``cdm_sample_prologue_sub`` turns it into the
+    timestep; ``cdm_dpmpp_step`` applies the update and keeps the previous data prediction in ``dprev``, allocated here
+    once so a captured graph stays valid across runs (its stale contents are never read: c1 = 0 at the first position).
+    The solver is deterministic: no z in any ``z_source``.  CPU-RNG order, for p = S..1: the shortcut row(s), cond
+    before uncond, and nothing else.  Snapshots: ``snapshot_slots(S, save_rate)`` on positions."""
+
+    def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
+                 steps=20, order: int = 2, spacing="uniform", save_rate: int = 20, z_source: str = "device",
+                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True):
+        self.taus = timestep_subsequence(sched.T, steps, spacing)
+        self.S = len(self.taus)
+        tables = dpmpp_tables(sched.ab_t, self.taus, order)               # validates order before anything is allocated
+        self.order = int(order)
+        super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, positions=self.S)
+        dev = self.dev
+        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
+        self.tables = tuple(torch.from_numpy(v).to(dev) for v in tables)  # sq, ra, c0, c1, cx, cd
+        self.cur_k = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.dprev = torch.empty(n * self.H * self.H, device=dev)
+
+    def _needs_z_table(self):
+        return False
+
+    def prepare_rng(self, host_z: bool):
+        self.sc_table.copy_(torch.stack([self._draw_shortcut_row() for _ in range(self.S)]))
+
+    def _step(self, s):
+        lb = lib()
+        nf, n = self.model.n_feat, self.n
+        lb.cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
+                                   _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+        half = self.sets * nf
+        sc_w, sc_b = self.sc_cur[:half], self.sc_cur[half:]
+        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, sc_w, sc_b, n, s)
+        numel = n * self.H * self.H
+        lb.cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                          1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.S,
+                          _p(self.dprev), _p(self.slot), _p(self.snaps), s)
+
+
 class DDPM:
     """Script-globals bundle of the reference (nn_model, timesteps, b_t/a_t/ab_t, n_cfeat, device)."""
 
@@ -460,16 +563,23 @@ class DDPM:
     def denoise_add_noise(self, x, t, pred_noise, z=None):
         return denoise_add_noise(x, t, pred_noise, z, self.sched)
 
-    def _sampler(self, n, guide_w, params, save_rate, ddim=None):
-        """The cached sampler of a configuration; ``ddim = (steps, eta, spacing)`` selects the strided one."""
+    def _sampler(self, n, guide_w, params, save_rate, ddim=None, dpm=None):
+        """The cached sampler of a configuration; ``ddim = (steps, eta, spacing)`` selects the strided one,
+        ``dpm = (steps, order, spacing)`` the multistep one (its key starts with a tag no DDIM key holds)."""
         key = (n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, self.z_source)
         if ddim is not None:
             steps, eta, spacing = ddim
             key += (steps, float(eta), spacing if isinstance(spacing, str) else tuple(spacing))
+        elif dpm is not None:
+            steps, order, spacing = dpm
+            key += ("dpmpp", steps, order, spacing if isinstance(spacing, str) else tuple(spacing))
         smp = self._samplers.get(key)
         if smp is None and ddim is not None:
             smp = self._samplers[key] = DDIMSampler(self.model, self.sched, n, guide_w, params, steps, eta, spacing,
                                                     save_rate, self.z_source, seed=self.seed)
+        elif smp is None and dpm is not None:
+            smp = self._samplers[key] = DPMSolverSampler(self.model, self.sched, n, guide_w, params, steps, order,
+                                                         spacing, save_rate, self.z_source, seed=self.seed)
         elif smp is None:
             smp = self._samplers[key] = GraphSampler(self.model, self.sched, n, guide_w, params, save_rate,
                                                      self.z_source, seed=self.seed)
@@ -522,20 +632,50 @@ class DDPM:
         smp.prepare_rng(host_z=self.z_source == "host")
         return smp.run(noise_images)
 
+    @torch.no_grad()
+    def sample_dpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=20, order=2,
+                   spacing="uniform", save_rate=20):
+        """sample_ddpm on ``steps`` of the T timesteps with the second-order multistep update (:class:`DPMSolverSampler`;
+        ``order=1``: first order throughout; ``spacing`` as in :meth:`sample_ddim`) -> (samples, intermediate).  x_T and
+        random params consume the CPU RNG as sample_ddpm does; the run is deterministic given x_T and the shortcut
+        draws.  Snapshots: snapshot_slots(steps, save_rate) on positions."""
+        assert size == self.model.h
+        x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
+        if params is None:
+            params = torch.rand(n_sample, self.n_cfeat)
+        smp = self._sampler(n_sample, guide_w, params, save_rate, dpm=(steps, order, spacing))
+        smp.prepare_rng(host_z=self.z_source == "host")
+        return smp.run(x_T)
+
+    @torch.no_grad()
+    def sample_dpm_from_noise(self, noise_images, params=None, steps=20, order=2, spacing="uniform", save_rate=20,
+                              guide_w=0.0):
+        """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_dpm`)."""
+        n = noise_images.shape[0]
+        smp = self._sampler(n, guide_w, params, save_rate, dpm=(steps, order, spacing))
+        smp.prepare_rng(host_z=self.z_source == "host")
+        return smp.run(noise_images)
+
 
 @torch.no_grad()
 def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.0, timesteps=1000, b_t=None,
-                a_t=None, ab_t=None, z_source="device", *, steps=None, eta=0.0, spacing="uniform"):
+                a_t=None, ab_t=None, z_source="device", *, steps=None, eta=0.0, spacing="uniform", solver="ddim",
+                order=2):
     """Functional sampler of code/sample_power_spectra.py:71-110 (returns the final x only).  b_t / a_t / ab_t are
     the caller's schedule, as in the reference (all three or none: None builds the default schedule).
     ``steps`` (keyword only; None: the reference's T-step ancestral sampler) runs DDPM.sample_ddim with ``eta`` and
-    ``spacing`` on that many of the timesteps."""
+    ``spacing`` on that many of the timesteps, or, with ``solver="dpmpp"``, DDPM.sample_dpm with ``order`` and ``spacing``
+    (``solver`` is only consulted when ``steps`` is given)."""
     given = [v is not None for v in (b_t, a_t, ab_t)]
     if any(given) and not all(given):
         raise ValueError("pass all of b_t, a_t, ab_t or none of them")
     d = DDPM(model, timesteps, device or model.out[3].weight.device, z_source=z_source,
              sched_tensors=(b_t, a_t, ab_t) if all(given) else None)
     if steps is not None:
+        if solver == "dpmpp":
+            return d.sample_dpm(n_sample, size, device, params, guide_w, steps, order, spacing)[0]
+        if solver != "ddim":
+            raise ValueError(f"solver must be 'ddim' or 'dpmpp', got {solver!r}")
         return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing)[0]
     if params is None:
         x_T = torch.randn(n_sample, 1, size, size)

@@ -33,6 +33,9 @@ Training for guided sampling (all off by default; without them the outputs are t
   --sample-steps S [--eta E] [--spacing uniform|quadratic]
                  run the sampling at the end on S of the TIMESTEPS with the strided DDIM sampler (eta 0: deterministic)
                  instead of all of them; the log lines then name steps=S, eta=E.
+  --sample-steps S --sampler dpmpp [--solver-order 1|2] [--spacing ...]
+                 the same S timesteps with the second-order multistep solver (DPM-Solver++ 2M, deterministic; order 1
+                 is its first-order form); the log lines then name steps=S, dpmpp order=O.  Not with a non-zero --eta.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -80,9 +83,16 @@ def main(argv=None):
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0 deterministic, 1 ancestral variance)")
     ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform",
                     help="how --sample-steps picks its timesteps")
+    ap.add_argument("--sampler", choices=["ddim", "dpmpp"], default="ddim",
+                    help="the update --sample-steps uses: strided DDIM, or the multistep DPM-Solver++ (2M)")
+    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="order of --sampler dpmpp")
     a = ap.parse_args(argv)
     if a.sample_steps < 0 or a.sample_steps > a.timesteps:
         ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
+    if a.sampler == "dpmpp" and a.sample_steps == 0:
+        ap.error("--sampler dpmpp needs --sample-steps S")
+    if a.sampler == "dpmpp" and a.eta != 0:
+        ap.error("--sampler dpmpp is deterministic: it takes no --eta")
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -226,9 +236,16 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
     noise = torch.randn(x.shape, device=dev)
     x_T = cdm_amd.perturb_input(x, a.timesteps, noise, d.sched)
     t0 = time.time()
-    ddim = dict(steps=a.sample_steps, eta=a.eta, spacing=a.spacing) if a.sample_steps > 0 else None
-    how = f"T={a.timesteps}" + (f", steps={a.sample_steps}, eta={a.eta:g}" if ddim else "")
-    if ddim:
+    dpm = ddim = None
+    if a.sample_steps > 0 and a.sampler == "dpmpp":
+        dpm = dict(steps=a.sample_steps, order=a.solver_order, spacing=a.spacing)
+    elif a.sample_steps > 0:
+        ddim = dict(steps=a.sample_steps, eta=a.eta, spacing=a.spacing)
+    how = f"T={a.timesteps}" + (f", steps={a.sample_steps}, eta={a.eta:g}" if ddim else "") \
+        + (f", steps={a.sample_steps}, dpmpp order={a.solver_order}" if dpm else "")
+    if dpm:
+        rec, inter = d.sample_dpm_from_noise(x_T, p, guide_w=a.guide_w, **dpm)
+    elif ddim:
         rec, inter = d.sample_ddim_from_noise(x_T, p, guide_w=a.guide_w, **ddim)
     else:
         rec, inter = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w)
@@ -243,7 +260,9 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
     cdm_amd.compare_power_spectra(x, rec, out_dir)
     if conditional:
         t0 = time.time()
-        if ddim:
+        if dpm:
+            samples, _ = d.sample_dpm(ns, H, dev, p, a.guide_w, **dpm)
+        elif ddim:
             samples, _ = d.sample_ddim(ns, H, dev, p, a.guide_w, **ddim)
         else:
             samples, _ = d.sample_ddpm(ns, H, dev, p, a.guide_w)

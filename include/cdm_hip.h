@@ -415,7 +415,20 @@ int cdm_ddim_step(const float* xin, float* x, float* x2, long long numel, const 
                   const int* cur_i, const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
                   const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
                   const int* snap_slot, float* snaps, void* stream);
-/* randn_like / randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
+/* second-order multistep (DPM-Solver++ 2M) update at the position k = *cur_k of the same subsequence, with separate fp32
+ * roundings in this order (eps = eu + w (ec - eu) when cfg):
+ *   d = (x - sq[k] eps) * ra[k];  D = d when c1[k] == 0, else c0[k] d + c1[k] dprev;  x <- cx[k] x + cd[k] D;  dprev <- d
+ * sq / ra / c0 / c1 / cx / cd [npos + 1] are host-built tables (sigma_i, 1 / alpha_i, the multistep weights, sigma_j /
+ * sigma_i, alpha_j (1 - e^-h)).  dprev (numel floats, required) is written at every position and read only where
+ * c1[k] != 0, so it may be uninitialised at the first position.  No z is read or drawn.  Writes x (and both halves of x2
+ * when given; x2 may alias x), and the snapshot slot snap_slot[k] (snap_slot [npos + 1], optional) of snaps when >= 0.
+ * A k outside 1..npos writes nothing.  hipErrorInvalidValue, nothing launched: a required pointer null, npos < 1,
+ * numel < 0, snap_slot without snaps. */
+int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                   const int* cur_k, const float* sq, const float* ra, const float* c0, const float* c1,
+                   const float* cx, const float* cd, int npos, float* dprev, const int* snap_slot, float* snaps,
+                   void* stream);
+/* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
 int cdm_philox_normal(float* out, long long n, unsigned long long seed, unsigned int sub, const int* sub_dev,
