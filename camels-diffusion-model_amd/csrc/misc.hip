@@ -1080,51 +1080,128 @@ __global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long lo
 // The one deliberate difference: sqrtf here is correctly rounded; torch's vectorised CPU sqrt is not always
 // (<= 1 ulp), so p differs from torch CPU by <= 1 ulp of the update on those elements (test_gpu_trainer.py).
 // ------------------------------------------------------------------------------------------------
-__global__ void adam_prep_kernel(double* state, const double* bc, int nbc) {
+static __device__ __forceinline__ void adam_prep(double* state, const double* bc, int nbc) {
     const double step = state[1] + 1.0;
     state[1] = step;
     const int k = (int)(step < (double)nbc ? step : (double)nbc) - 1;
     state[2] = (double)(float)(-(state[0] / bc[2 * k]));     // value=-step_size, Scalar -> float
     state[3] = (double)(float)bc[2 * k + 1];                  // bias_correction2_sqrt, wrapped scalar -> float
 }
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, const double* state, float beta1c,
-                            float beta2, float beta2c, float eps, float gscale) {
+__global__ void adam_prep_kernel(double* state, const double* bc, int nbc) { adam_prep(state, bc, nbc); }
+// One kernel for the four forms.
+// EMA: the exponential moving average of the parameters in the same pass (p is in registers: a separate EMA kernel
+// would read the 86.5 MB of p again).  ema += (1 - decay) (p_new - ema) as one fmaf; decay is a device double (like lr
+// in state), so a captured step follows set_ema_decay without re-capture.  decay == 0 copies p: fl(fl(p - e) + e) is
+// not always p (p - e is inexact once |p| falls to the size of an update).
+// CLIP: the global-norm clip coefficient and the skip flag of clip_prep_kernel, read from its device record
+// {norm, coef, skip}.  gi = (g * gscale) * coef, two fp32 roundings (with gscale = 1, torch's g.mul_(clip_coef) of
+// clip_grad_norm_); g is in a register here, a scaling pass of its own would read and write its 86.5 MB once more.
+// skip != 0 (a non-finite gradient): every thread returns before it touches p, m, v, ema; the branch is uniform.
+// The Adam expressions are the same source lines in every form, under one contract(off): p, m, v of <EMA, false>
+// are bit-identical to <false, false>, and <*, true> at coef == 1 to <*, false>.
+template <bool EMA, bool CLIP>
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,
+                            const double* ema_decay, const double* clip_rec, float beta1c, float beta2, float beta2c,
+                            float eps, float gscale) {
 #pragma clang fp contract(off)  // only the explicit fmaf below fuse, as in torch's CPU kernels
+    float coef = 1.0f;
+    if constexpr (CLIP) {
+        if (clip_rec[2] != 0.0) return;
+        coef = (float)clip_rec[1];
+    }
     const float nss = (float)state[2], bc2s = (float)state[3];
+    float omd = 0.f;
+    if constexpr (EMA) omd = (float)(1.0 - *ema_decay);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;             // 1/world for the summed data-parallel gradient
+        float gi = g[i] * gscale;                         // 1/world for the summed data-parallel gradient
+        if constexpr (CLIP) gi = gi * coef;
         float mi = m[i];
         mi = fmaf(beta1c, gi - mi, mi);                   // exp_avg.lerp_(grad, 1 - beta1)
         float vi = v[i] * beta2;                          // exp_avg_sq.mul_(beta2)
         vi = fmaf(beta2c * gi, gi, vi);                   //   .addcmul_(grad, grad, 1 - beta2)
         const float denom = sqrtf(vi) / bc2s + eps;       // (exp_avg_sq.sqrt() / bc2_sqrt).add_(eps)
-        p[i] = p[i] + (nss * mi) / denom;                 // param.addcdiv_(exp_avg, denom, -step_size)
-        m[i] = mi; v[i] = vi;
-    }
-}
-// adam_kernel + the exponential moving average of the parameters in the same pass (p is in registers: a separate EMA
-// kernel would read the 86.5 MB of p again).  The Adam expressions are adam_kernel's, line for line, under the same
-// contract(off): p, m, v come out bit-identical.  ema += (1 - decay) (p_new - ema) as one fmaf; decay is a device
-// double (like lr in state), so a captured step follows set_ema_decay without re-capture.  decay == 0 copies p:
-// fl(fl(p - e) + e) is not always p (p - e is inexact once |p| falls to the size of an update).
-__global__ void adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,
-                                const double* ema_decay, float beta1c, float beta2, float beta2c, float eps, float gscale) {
-#pragma clang fp contract(off)  // only the explicit fmaf below fuse, as in torch's CPU kernels
-    const float nss = (float)state[2], bc2s = (float)state[3];
-    const float omd = (float)(1.0 - *ema_decay);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        float mi = m[i];
-        mi = fmaf(beta1c, gi - mi, mi);
-        float vi = v[i] * beta2;
-        vi = fmaf(beta2c * gi, gi, vi);
-        const float denom = sqrtf(vi) / bc2s + eps;
-        const float pn = p[i] + (nss * mi) / denom;
+        const float pn = p[i] + (nss * mi) / denom;       // param.addcdiv_(exp_avg, denom, -step_size)
         p[i] = pn;
         m[i] = mi; v[i] = vi;
-        const float ei = ema[i];
-        ema[i] = omd == 1.0f ? pn : fmaf(omd, pn - ei, ei);
+        if constexpr (EMA) {
+            const float ei = ema[i];
+            ema[i] = omd == 1.0f ? pn : fmaf(omd, pn - ei, ei);
+        }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ in front of optim.step()) and the non-finite
+// step skip, on the device: sum of squares of the flat gradient -> {norm, coef, skip} -> adam_kernel<*, true>.
+// Deterministic: per-thread fp64 sums over a fixed element set, fixed-order wave / block folds, one plain store per
+// block into a caller-owned slab, and one block that sums the slab in a fixed order.  No atomics, no hand-off
+// between blocks inside a launch; the block count is a function of n alone (grad_sumsq_blocks).
+// ------------------------------------------------------------------------------------------------
+constexpr int SUMSQ_MAX_BLOCKS = 2048;                   // == CDM_GRAD_SUMSQ_MAX_PARTIALS (cdm_hip.h)
+static inline int grad_sumsq_blocks(long long n) { return nblocks(n, 256 * 16, SUMSQ_MAX_BLOCKS); }
+
+static __device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// partial[blockIdx.x] = sum over this block's elements of (double)g * (double)g.  The base needs 4-byte alignment
+// only: `head` elements up to the first 16-byte boundary and the `n - head` mod 4 after the last float4 go to the
+// first threads of block 0; the float4 body is a grid-stride loop, four loads in flight per thread.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
+                                                         double* __restrict__ partial) {
+    const long long mis = (long long)((16 - (reinterpret_cast<unsigned long long>(g) & 15)) & 15) >> 2;
+    const long long head = mis < n ? mis : n;
+    const long long nq = (n - head) >> 2;               // float4 pieces of the aligned body
+    const float4* __restrict__ b4 = reinterpret_cast<const float4*>(g + head);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    auto sq4 = [](double a, const float4 v) {
+        a = fma((double)v.x, (double)v.x, a); a = fma((double)v.y, (double)v.y, a);
+        a = fma((double)v.z, (double)v.z, a); a = fma((double)v.w, (double)v.w, a);
+        return a;
+    };
+    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; q + 3 * stride < nq; q += 4 * stride) {
+        const float4 v0 = b4[q], v1 = b4[q + stride], v2 = b4[q + 2 * stride], v3 = b4[q + 3 * stride];
+        a0 = sq4(a0, v0); a1 = sq4(a1, v1); a2 = sq4(a2, v2); a3 = sq4(a3, v3);
+    }
+    for (; q < nq; q += stride) a0 = sq4(a0, b4[q]);
+    if (blockIdx.x == 0) {
+        const long long t = threadIdx.x, tail0 = head + (nq << 2);
+        if (t < head) { const double x = g[t]; a1 = fma(x, x, a1); }
+        if (tail0 + t < n) { const double x = g[tail0 + t]; a2 = fma(x, x, a2); }
+    }
+    __shared__ double red[4];
+    const double s = wave_sum_d((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// One block: S = sum of the nb partials (thread t takes t, t + 256, ... in order, then a fixed LDS tree),
+// norm = sqrt(S) gscale, skip = !isfinite(S) (an fp32 square cannot overflow fp64: S is non-finite exactly when an
+// element is), coef = (float)min(1, max_norm / (norm + 1e-6)); rec = {norm, coef, skip}.  skip: *skipped += 1 and the
+// Adam step count stays; otherwise adam_prep_kernel's work.
+__global__ __launch_bounds__(256) void clip_prep_kernel(const double* partial, int nb, double gscale,
+                                                        const double* max_norm, double* rec, int* skipped,
+                                                        double* state, const double* bc, int nbc) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double S = red[0];
+    const double norm = sqrt(S) * gscale;
+    const bool skip = !isfinite(S);
+    const float coef = (float)fmin(1.0, *max_norm / (norm + 1e-6));
+    rec[0] = norm; rec[1] = (double)coef; rec[2] = skip ? 1.0 : 0.0;
+    if (skip) *skipped += 1;
+    else adam_prep(state, bc, nbc);
 }
 
 // Context dropout for classifier-free guidance: c_out[b][:] = u[b] < p_drop ? 0 : c[b][:], u[b] element b of the
@@ -1477,14 +1554,31 @@ CDM_API int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long nume
                        cur_k, sq, ra, c0, c1, cx, cd, npos, dprev, snap_slot, snaps);
     return cdm_status();
 }
+static int adam_launch(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,
+                       const double* ema_decay, const double* clip_rec, double beta1, double beta2, double eps,
+                       float grad_scale, hipStream_t s) {
+    const dim3 grid(nblocks(n, 256, 16384)), block(256);
+    const float b1c = (float)(1.0 - beta1), b2 = (float)beta2, b2c = (float)(1.0 - beta2), e = (float)eps;
+    if (ema && clip_rec)
+        hipLaunchKernelGGL((adam_kernel<true, true>), grid, block, 0, s, p, g, m, v, ema, n, state, ema_decay, clip_rec,
+                           b1c, b2, b2c, e, grad_scale);
+    else if (ema)
+        hipLaunchKernelGGL((adam_kernel<true, false>), grid, block, 0, s, p, g, m, v, ema, n, state, ema_decay, clip_rec,
+                           b1c, b2, b2c, e, grad_scale);
+    else if (clip_rec)
+        hipLaunchKernelGGL((adam_kernel<false, true>), grid, block, 0, s, p, g, m, v, ema, n, state, ema_decay, clip_rec,
+                           b1c, b2, b2c, e, grad_scale);
+    else
+        hipLaunchKernelGGL((adam_kernel<false, false>), grid, block, 0, s, p, g, m, v, ema, n, state, ema_decay,
+                           clip_rec, b1c, b2, b2c, e, grad_scale);
+    return cdm_status();
+}
 CDM_API int cdm_adam(float* p, const float* g, float* m, float* v, long long n, double* state, const double* bc,
                      int nbc, double beta1, double beta2, double eps, float grad_scale, void* stream) {
     if (nbc < 1) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, S(stream), state, bc, nbc);
     int e = cdm_status(); if (e) return e;
-    hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n, 256, 16384)), dim3(256), 0, S(stream), p, g, m, v, n, state,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, grad_scale);
-    return cdm_status();
+    return adam_launch(p, g, m, v, nullptr, n, state, nullptr, nullptr, beta1, beta2, eps, grad_scale, S(stream));
 }
 CDM_API int cdm_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state,
                          const double* bc, int nbc, double beta1, double beta2, double eps, float grad_scale,
@@ -1492,9 +1586,30 @@ CDM_API int cdm_adam_ema(float* p, const float* g, float* m, float* v, float* em
     if (nbc < 1 || n < 0 || !ema || !ema_decay) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, S(stream), state, bc, nbc);
     int e = cdm_status(); if (e || n == 0) return e;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(nblocks(n, 256, 16384)), dim3(256), 0, S(stream), p, g, m, v, ema, n, state,
-                       ema_decay, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, grad_scale);
+    return adam_launch(p, g, m, v, ema, n, state, ema_decay, nullptr, beta1, beta2, eps, grad_scale, S(stream));
+}
+CDM_API int cdm_grad_sumsq(const float* g, long long n, double* partial, int* nb_out, void* stream) {
+    if (!partial || n < 0 || (n > 0 && !g) || (reinterpret_cast<unsigned long long>(g) & 3))
+        return (int)hipErrorInvalidValue;
+    const int nb = grad_sumsq_blocks(n);
+    if (nb_out) *nb_out = nb;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, S(stream), g, n, partial);
     return cdm_status();
+}
+CDM_API int cdm_adam_clipped(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state,
+                             const double* bc, int nbc, double beta1, double beta2, double eps, float grad_scale,
+                             const double* ema_decay, const double* max_norm, double* partial, double* clip_rec,
+                             int* skipped, void* stream) {
+    if (!p || !g || !m || !v || !state || !bc || !max_norm || !partial || !clip_rec || !skipped || n < 0 || nbc < 1 ||
+        (ema != nullptr) != (ema_decay != nullptr) || (reinterpret_cast<unsigned long long>(g) & 3))
+        return (int)hipErrorInvalidValue;
+    const int nb = grad_sumsq_blocks(n);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, S(stream), g, n, partial);
+    int e = cdm_status(); if (e) return e;
+    hipLaunchKernelGGL(clip_prep_kernel, dim3(1), dim3(256), 0, S(stream), partial, nb, (double)grad_scale, max_norm,
+                       clip_rec, skipped, state, bc, nbc);
+    e = cdm_status(); if (e || n == 0) return e;
+    return adam_launch(p, g, m, v, ema, n, state, ema_decay, clip_rec, beta1, beta2, eps, grad_scale, S(stream));
 }
 CDM_API int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsigned long long seed, unsigned int sub,
                              const int* sub_dev, float* c_out, int* keep, void* stream) {

@@ -30,6 +30,10 @@ Training for guided sampling (all off by default; without them the outputs are t
                  c = 0 forward of classifier-free guidance (--guide-w > 0) is one the model was trained on.
   --ema DECAY    keep an exponential moving average of the parameters; the sampling at the end runs on it, and every
                  model_epoch_N.pth gets a model_epoch_N_ema.pth beside it.
+  --clip-grad NORM
+                 clip the global L2 norm of the gradient to NORM before every Adam update (clip_grad_norm_ semantics,
+                 computed on the device inside the captured step; inf: no scaling) and skip a step whose gradient holds
+                 a NaN / inf; the epoch line then ends with the last gradient norm and the count of skipped steps.
   --sample-steps S [--eta E] [--spacing uniform|quadratic]
                  run the sampling at the end on S of the TIMESTEPS with the strided DDIM sampler (eta 0: deterministic)
                  instead of all of them; the log lines then name steps=S, eta=E.
@@ -76,6 +80,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--p-uncond", type=float, default=0.0, help="context dropout probability (train the c = 0 branch)")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep and sample from EMA weights")
+    ap.add_argument("--clip-grad", type=float, default=None, metavar="NORM",
+                    help="clip the gradient's global L2 norm to NORM; skip steps with a non-finite gradient")
     ap.add_argument("--resume", default=None, metavar="PATH",
                     help="write trainer_epoch_N.pt checkpoints; continue from PATH if it exists")
     ap.add_argument("--sample-steps", type=int, default=0, metavar="S",
@@ -89,6 +95,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.sample_steps < 0 or a.sample_steps > a.timesteps:
         ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
+    if a.clip_grad is not None and not a.clip_grad > 0:
+        ap.error("--clip-grad must be > 0 (inf: report the norm and skip non-finite steps only)")
     if a.sampler == "dpmpp" and a.sample_steps == 0:
         ap.error("--sampler dpmpp needs --sample-steps S")
     if a.sampler == "dpmpp" and a.eta != 0:
@@ -146,7 +154,8 @@ def main(argv=None):
     # ------------------------------- model / trainer -------------------------------
     torch.manual_seed(a.seed)
     model = ContextUnet(1, a.n_feat, n_cfeat, H).to(dev)
-    trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed, ema_decay=a.ema, p_uncond=a.p_uncond)
+    trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed, ema_decay=a.ema, p_uncond=a.p_uncond,
+                      clip_grad_norm=a.clip_grad)
     log = open(os.path.join(out_dir, "timing_and_performance.log"), "a") if rank == 0 else None
     loss_log, val_log = [], []
     first_ep = 0
@@ -184,6 +193,8 @@ def main(argv=None):
         ep_time = time.time() - t_ep
         loss_log.append(float(ep_loss.item()) / max(nb, 1))
         msg = f"Epoch {ep + 1}/{a.epochs}, Train Loss: {loss_log[-1]:.6f}, lr {lr:.3e}, epoch time {ep_time:.2f}s"
+        if a.clip_grad is not None:                  # read where check_finite was read: still one sync point per epoch
+            msg += f", grad norm {float(trainer.grad_norm.item()):.4e}, skipped steps {trainer.check_skipped()}"
         if conditional and (ep % 5 == 0 or ep == a.epochs - 1) and len(test_idx):
             val_log.append(validation_mse(model, maps_d[test_idx.to(dev)], params_d[test_idx.to(dev)], trainer.sched,
                                           a.timesteps, a.batch_size))

@@ -14,6 +14,8 @@ MI355X design:
     context is zeroed with that probability, one more Philox draw inside the step), an exponential moving average of
     the parameters kept by the fused Adam kernel (ema_decay; ema_weights() / ema_state_dict() to sample from it), and
     state_dict() / load_state_dict() that continue a run bit-identically;
+  * optional, off by default: global-norm gradient clipping and a non-finite step skip (clip_grad_norm), computed on
+    the device inside the captured step (see Trainer);
   * data parallel: one process per GPU; each rank trains on its own shard of the global batch; the
     flat gradient buffer is laid out in backward-completion order and cut into stage buckets that are
     all-reduced (RCCL over xGMI) asynchronously as soon as the engine reports a stage complete, so the
@@ -24,6 +26,7 @@ MI355X design:
 from __future__ import annotations
 
 import contextlib
+import struct
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -86,13 +89,28 @@ class GradBucketer:
 class Trainer:
     def __init__(self, model, lrate: float, timesteps: int, batch_size: int, seed: int = 0,
                  use_graph: bool = True, group=None, broadcast_buffers: bool = True, force_ddp: bool = False,
-                 ema_decay: Optional[float] = None, p_uncond: float = 0.0):
+                 ema_decay: Optional[float] = None, p_uncond: float = 0.0, clip_grad_norm: Optional[float] = None):
         """``force_ddp``: take the data-parallel path (stage-bucketed async all-reduce, rank-0 broadcasts, eager
         steps) even in a one-rank process group — RCCL readiness on a one-GPU box (tests/test_gpu_rccl.py).
         ``ema_decay``: keep ``self.ema``, an exponential moving average of the parameters, updated inside the fused
         Adam kernel (ema += (1 - decay) (p - ema) after every step; starts as a copy of the parameters).
         ``p_uncond``: probability with which a sample's context is replaced by the null condition c = 0 in a step
-        (the condition the guided samplers evaluate; the reference never trains it)."""
+        (the condition the guided samplers evaluate; the reference never trains it).
+        ``clip_grad_norm``: ``None`` (default) launches exactly the unguarded step.  A value > 0 puts
+        ``torch.nn.utils.clip_grad_norm_(parameters, value)`` in front of the Adam update, on the device and inside
+        the captured step: the global L2 norm of the flat gradient (fp64, deterministic: a fixed-order sum, no
+        atomics), the coefficient ``clip_coef(norm, value)`` folded into the fused Adam kernel, and a skip flag.
+        ``float("inf")`` never scales (the coefficient is exactly 1: the trajectory is the unguarded one) and keeps
+        the norm report and the skip.  A step whose gradient holds a NaN / inf is skipped: parameters, Adam moments,
+        Adam step count and EMA stay untouched, ``self.skipped`` (device int) rises by one; the Philox counter and
+        ``self.steps`` still advance, so the next step draws fresh noise.  BatchNorm running statistics are NOT
+        protected: the forward that overflowed has already written them.  ``self.grad_norm`` is the device fp64 norm
+        of the last step's gradient before clipping; ``check_skipped()`` reads the counter (one host sync, per epoch).
+        Data parallel: the norm is taken after the last all-reduce, of the summed buffer times 1 / world, the averaged
+        gradient Adam sees; every rank holds identical bytes there, so every rank computes the same norm, coefficient
+        and skip decision without another collective."""
+        if clip_grad_norm is not None:
+            _check_max_norm(clip_grad_norm)
         if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1], got {ema_decay}")
         if not 0.0 <= float(p_uncond) <= 1.0:
@@ -157,6 +175,14 @@ class Trainer:
         self.ema_decay = None if ema_decay is None else torch.tensor([float(ema_decay)], dtype=torch.float64, device=dev)
         self.p_uncond = float(p_uncond)
         self._in_ema = False          # inside ema_weights(): flat holds the EMA, a step would train it
+        # ---- gradient clipping / step skip: device max_norm (like lr: captured steps follow it), the sum-of-squares
+        #      partials, the record {norm, coef, skip} of the last step and the skipped-step counter ----
+        self.clip = clip_grad_norm is not None
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.clip:
+            self.max_norm = torch.tensor([float(clip_grad_norm)], dtype=torch.float64, device=dev)
+            self.clip_partial = torch.zeros(GRAD_SUMSQ_MAX_PARTIALS, dtype=torch.float64, device=dev)
+            self.clip_rec = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64, device=dev)
         # ---- optimizer state on device (fp64, as torch keeps lr / step as Python floats):
         #      [lr, step, -step_size, sqrt(bc2)] + the host-evaluated bias-correction table ----
         self.betas, self.eps = (0.9, 0.999), 1e-8
@@ -210,6 +236,28 @@ class Trainer:
         if not 0.0 <= float(decay) <= 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1], got {decay}")
         self.ema_decay.fill_(float(decay))
+
+    def set_clip_grad_norm(self, max_norm: float):
+        """New clipping threshold from the next step on (a device double, like lr: captured steps follow it)."""
+        if not self.clip:
+            raise RuntimeError("this Trainer does not clip gradients (clip_grad_norm=None)")
+        _check_max_norm(max_norm)
+        self.max_norm.fill_(float(max_norm))
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """Device fp64 scalar: the global L2 norm of the last step's (averaged) gradient, before clipping."""
+        if not self.clip:
+            raise RuntimeError("this Trainer does not clip gradients (clip_grad_norm=None)")
+        return self.clip_rec[0]
+
+    def check_skipped(self, reset: bool = True) -> int:
+        """Number of steps since the last check that were skipped for a NaN / inf gradient (always 0 without
+        clip_grad_norm).  One host sync: call it once per epoch, not per step."""
+        n = int(self.skipped.item())
+        if reset and n:
+            self.skipped.zero_()
+        return n
 
     def check_finite(self, reset: bool = True) -> int:
         """Number of steps since the last check whose loss was NaN / inf (SURVEY §5 failure guard).  One host sync:
@@ -267,6 +315,7 @@ class Trainer:
             "steps": int(self.steps), "seed": int(self.seed),
             "ema_decay": None if self.ema is None else float(self.ema_decay.item()),
             "p_uncond": float(self.p_uncond),
+            "clip_grad_norm": float(self.max_norm.item()) if self.clip else None, "skipped": cpu(self.skipped),
         }
 
     def load_state_dict(self, sd: Dict[str, object]):
@@ -276,6 +325,10 @@ class Trainer:
             raise ValueError("the checkpoint has EMA weights and the trainer was built with ema_decay=None"
                              if self.ema is None else
                              "the trainer keeps EMA weights and the checkpoint has none")
+        if (sd.get("clip_grad_norm") is not None) != self.clip:     # checkpoints from before the option: off
+            raise ValueError("the checkpoint clips gradients and the trainer was built with clip_grad_norm=None"
+                             if not self.clip else
+                             "the trainer clips gradients and the checkpoint was written without clipping")
         if list(sd["layout"]) != list(self.offsets):
             raise ValueError("checkpoint holds a different parameter list than this model")
         own = self.model.state_dict()
@@ -298,6 +351,12 @@ class Trainer:
                 self.ema.copy_(sd["ema"])
                 self.ema_decay.fill_(float(sd["ema_decay"]))
             self.opt_state.copy_(sd["opt_state"]); self.ctr.copy_(sd["ctr"]); self.nonfinite.copy_(sd["nonfinite"])
+            if self.clip:
+                self.max_norm.fill_(float(sd["clip_grad_norm"]))
+            if sd.get("skipped") is not None:
+                self.skipped.copy_(sd["skipped"])
+            else:
+                self.skipped.zero_()
         self.steps = int(sd["steps"])
         if int(sd["seed"]) != self.seed or float(sd["p_uncond"]) != self.p_uncond:
             self.seed, self.p_uncond = int(sd["seed"]), float(sd["p_uncond"])
@@ -339,7 +398,12 @@ class Trainer:
         self.eng.backward(sb.ws, P, sb.deps, self.grads, s, out3_bias_done=True, on_stage=hook)
         if self.ddp:
             self.bucketer.wait()
-        if self.ema is None:
+        if self.clip:              # norm of the (summed) buffer, coefficient and skip flag, then Adam: all on device
+            lb.cdm_adam_clipped(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), _p(self.ema), self.total,
+                                _p(self.opt_state), _p(self.adam_bc), self.adam_bc.shape[0], self.betas[0],
+                                self.betas[1], self.eps, 1.0 / self.world, _p(self.ema_decay), _p(self.max_norm),
+                                _p(self.clip_partial), _p(self.clip_rec), _p(self.skipped), s)
+        elif self.ema is None:
             lb.cdm_adam(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), self.total, _p(self.opt_state),
                         _p(self.adam_bc), self.adam_bc.shape[0], self.betas[0], self.betas[1], self.eps,
                         1.0 / self.world, s)
@@ -422,6 +486,22 @@ def shard_epoch(order: torch.Tensor, batch_size: int, world: int, rank: int):
         n = R // world + (1 if rank < R % world else 0)
         out.append((part[lo:lo + n], R))
     return out
+
+
+GRAD_SUMSQ_MAX_PARTIALS = 2048     # CDM_GRAD_SUMSQ_MAX_PARTIALS (include/cdm_hip.h): doubles cdm_adam_clipped may write
+
+
+def _check_max_norm(v):
+    if not float(v) > 0.0:           # rejects <= 0 and NaN; inf passes
+        raise ValueError(f"clip_grad_norm must be > 0 (inf: report the norm and skip non-finite steps only), got {v}")
+
+
+def clip_coef(norm: float, max_norm: float) -> float:
+    """The factor the clipped Adam step multiplies the gradient with, as the device computes it
+    (torch.nn.utils.clip_grad_norm_'s clamp(max_norm / (total_norm + 1e-6), max=1.0), evaluated in fp64 and rounded
+    to fp32 once): float32(min(1.0, max_norm / (norm + 1e-6))).  max_norm = inf gives exactly 1.0."""
+    c = min(1.0, float(max_norm) / (float(norm) + 1e-6))
+    return struct.unpack("f", struct.pack("f", c))[0]
 
 
 def adam_bias_table(beta1: float, beta2: float, n: int = 40960) -> torch.Tensor:

@@ -452,6 +452,36 @@ int cdm_adam(float* p, const float* g, float* m, float* v, long long n, double* 
 int cdm_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state, const double* bc,
                  int nbc, double beta1, double beta2, double eps, float grad_scale, const double* ema_decay,
                  void* stream);
+/* Global-norm gradient clipping and the non-finite step skip (torch.nn.utils.clip_grad_norm_ in front of
+ * optim.step()), computed on the device so a captured step needs no host read.
+ * cdm_grad_sumsq: partial[b] = sum over block b's elements of (double)g[i] * (double)g[i], b < nb, plain stores.
+ * nb = clamp(ceil(n / 4096), 1, CDM_GRAD_SUMSQ_MAX_PARTIALS), a function of n alone; *nb_out (optional, a host int)
+ * receives it.  Every thread sums a fixed set of elements in fp64 and the wave / block folds have a fixed order: the
+ * partials, and any fixed-order sum of them, are the same bits in every run.  g needs 4-byte alignment only (a slice
+ * of a larger buffer): the elements before the first 16-byte boundary and after the last whole float4 are read one by
+ * one, the rest as float4.  n == 0 writes partial[0] = 0.  hipErrorInvalidValue, nothing launched: partial null,
+ * n < 0, g null with n > 0, g not 4-byte aligned. */
+#define CDM_GRAD_SUMSQ_MAX_PARTIALS 2048
+int cdm_grad_sumsq(const float* g, long long n, double* partial, int* nb_out, void* stream);
+/* cdm_adam / cdm_adam_ema behind that guard, three launches: cdm_grad_sumsq's kernel into partial (caller-owned,
+ * room for cdm_grad_sumsq's nb doubles; CDM_GRAD_SUMSQ_MAX_PARTIALS always suffices), one block that sums the
+ * partials in a fixed order to S and writes clip_rec (device double[3]) = {norm, coef, skip}:
+ *   norm = sqrt(S) * grad_scale                            fp64: the norm of the gradient Adam sees
+ *   skip = !isfinite(S)                                    1.0 / 0.0; S is non-finite exactly when an element of g is
+ *   coef = (float)min(1.0, *max_norm / (norm + 1e-6))      max_norm: device double[1] read at run time, like lr in
+ *                                                          state; +inf gives coef == 1 exactly
+ * and, if skip, adds 1 to *skipped (device int) and leaves state alone, otherwise advances state as cdm_adam does;
+ * then the Adam kernel with gi = (g[i] * grad_scale) * coef, two fp32 roundings, every other expression cdm_adam's
+ * (and cdm_adam_ema's for the EMA): at coef == 1 the results are cdm_adam's bits, at coef < 1 those of cdm_adam on
+ * the gradient (g * grad_scale) * coef with grad_scale 1.  If skip, the kernel returns before it reads or writes p, m,
+ * v, ema: parameters, moments, step count and EMA are untouched.  ema and ema_decay are optional, both or neither.
+ * n == 0: norm 0, coef 1, no skip, the step count advances, nothing else.  hipErrorInvalidValue, nothing launched:
+ * p, g, m, v, state, bc, max_norm, partial, clip_rec or skipped null; n < 0; nbc < 1; ema without ema_decay or
+ * ema_decay without ema; g not 4-byte aligned. */
+int cdm_adam_clipped(float* p, const float* g, float* m, float* v, float* ema, long long n, double* state,
+                     const double* bc, int nbc, double beta1, double beta2, double eps, float grad_scale,
+                     const double* ema_decay, const double* max_norm, double* partial, double* clip_rec, int* skipped,
+                     void* stream);
 /* context dropout (training for classifier-free guidance): u[b] = element b of what
  * cdm_philox_uniform(out, B, 0, 1, seed, sub, sub_dev) writes; c_out[b][:] = u[b] < p_drop ? 0 : c[b][:] for c, c_out
  * [B][ncf]; keep (optional, int [B]) = 0 where the row was dropped, else 1.  c_out must not be c.
