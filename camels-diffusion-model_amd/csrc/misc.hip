@@ -1062,6 +1062,57 @@ __global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long lo
     }
 }
 
+// Masked (inpainting) sampling: re-impose the known pixels on the state a step kernel has just written (replacement
+// conditioning; no reference op).  The step went from timestep i to j: j = i - 1 in the ancestral form
+// (cur_k / steps null, position = i of 1..T), j = steps[k - 1] in the strided form (position = k of 1..npos).
+//   kn = sab[j]*known + somab[j]*xi   (j >= 1)      kn = known   (j == 0: xi neither read nor drawn, no multiply)
+//   x  = m*kn + (1 - m)*x             each product and the sum its own fp32 rounding; m == 1 stores kn and m == 0 keeps x
+//                                     as they are (no 0 * inf, no signed-zero change: bit for bit; xi is not needed at m == 0)
+// m = mask[e % mask_numel] (a [1,1,H,W] mask serves the whole batch).  xi: row (fresh ? rows - position : 0) of xi_table
+// (rows = T or npos, the row order of the z tables) when given, else Philox keyed by (seed ^ *seed_dev) ^
+// KNOWN_NOISE_DOMAIN, stream (fresh ? j : 0).  The XOR moves the known-region noise to a key no z draw of the run uses
+// (z: key seed ^ *seed_dev, streams 1..T), so xi is independent of every z whatever the streams are; the constant is the
+// ASCII of "known_xi" and has no other meaning.
+// Writes x, both halves of the model-input buffer (x2 may alias x) and the snapshot slot of this position when >= 0 (the
+// step kernel stored the unblended state there).  A position outside its range, or i outside 1..T, writes nothing.
+constexpr unsigned long long KNOWN_NOISE_DOMAIN = 0x6B6E6F776E5F7869ull;
+__global__ void mask_blend_kernel(float* x, float* x2, long long numel, const float* known, const float* mask,
+                                  long long mask_numel, const int* cur_i, const int* cur_k, const int* steps, int npos,
+                                  int T, const float* sab, const float* somab, const float* xi_table, long long xistride,
+                                  int fresh, unsigned long long seed, const long long* seed_dev, const int* snap_slot,
+                                  float* snaps) {
+#pragma clang fp contract(off)  // separate fp32 roundings, as a torch CPU restatement computes them
+    const int i = *cur_i;
+    if (i < 1 || i > T) return;
+    int pos = i, rows = T, j = i - 1;
+    if (cur_k) {
+        pos = *cur_k; rows = npos;
+        if (pos < 1 || pos > npos) return;
+        j = steps[pos - 1];
+        if (j < 0 || j >= i) return;
+    }
+    const int slot = snap_slot ? snap_slot[pos] : -1;
+    const float sa = sab[j], so = somab[j];
+    const float* xr = xi_table ? xi_table + (fresh ? (long long)(rows - pos) * xistride : 0) : nullptr;
+    const unsigned long long sd = (seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed) ^ KNOWN_NOISE_DOMAIN;
+    const uint32_t sub = fresh ? (uint32_t)j : 0u;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
+        const float m = mask[e % mask_numel];
+        float v = x[e];
+        if (m != 0.f) {
+            float kn = known[e];
+            if (j >= 1) {
+                const float xi = xr ? xr[e] : philox_normal(sd, sub, e);
+                kn = sa * kn + so * xi;
+            }
+            v = (m == 1.f) ? kn : m * kn + (1.f - m) * v;
+        }
+        x[e] = v;
+        if (x2) { x2[e] = v; x2[numel + e] = v; }
+        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Adam =torch.optim.Adam's single-tensor step (torch/optim/adam.py _single_tensor_adam, the path the
 // reference's CPU run takes; code/train_diffusion_condition.py:200,229), with lr / step in device memory so
@@ -1552,6 +1603,21 @@ CDM_API int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long nume
     if (numel == 0) return 0;
     hipLaunchKernelGGL(dpmpp_step_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w,
                        cur_k, sq, ra, c0, c1, cx, cd, npos, dprev, snap_slot, snaps);
+    return cdm_status();
+}
+CDM_API int cdm_mask_blend(float* x, float* x2, long long numel, const float* known, const float* mask,
+                           long long mask_numel, const int* cur_i, const int* cur_k, const int* steps, int npos, int T,
+                           const float* sab, const float* somab, const float* xi_table, long long xistride, int fresh,
+                           unsigned long long seed, const long long* seed_dev, const int* snap_slot, float* snaps,
+                           void* stream) {
+    if (numel <= 0 || mask_numel <= 0 || numel % mask_numel != 0) return (int)hipErrorInvalidValue;
+    if (!x || !known || !mask || !cur_i || !sab || !somab || T < 1 || xistride < 0 || (snap_slot && !snaps))
+        return (int)hipErrorInvalidValue;
+    if (!cur_k || !steps) cur_k = nullptr, steps = nullptr;      // the ancestral form: j = *cur_i - 1
+    else if (npos < 1 || npos > T) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_blend_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), x, x2, numel, known, mask,
+                       mask_numel, cur_i, cur_k, steps, npos, T, sab, somab, xi_table, xistride, fresh, seed, seed_dev,
+                       snap_slot, snaps);
     return cdm_status();
 }
 static int adam_launch(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,

@@ -28,6 +28,11 @@ ancestral variance), on the same captured step graph; ``DDPM.sample_ddim`` / ``s
 second-order multistep update of :func:`dpmpp_tables` (DPM-Solver++ 2M: the previous step's data prediction is reused,
 no extra network evaluation); ``DDPM.sample_dpm`` / ``sample_dpm_from_noise`` and ``sample_ddpm(..., steps=S,
 solver="dpmpp")``.
+
+Masked (inpainting) sampling (not in the reference): every sampler above takes ``known=`` / ``mask=`` and then
+re-imposes the known pixels, noised to the level of the state (:func:`known_tables`), after every step with one more
+kernel on the step graph (``cdm_mask_blend``; :class:`GraphSampler` has the definition); ``DDPM.inpaint`` is the
+convenience entry point.
 """
 from __future__ import annotations
 
@@ -298,14 +303,85 @@ def dpmpp_tables(ab_t, taus, order: int = 2, dtype=np.float32):
     return tuple(out)
 
 
+def known_tables(ab_t):
+    """(sab, somab) of masked sampling: sqrt(ab_t) and sqrt(1 - ab_t), fp32 numpy arrays of T + 1 entries indexed by the
+    timestep; sab[0] = 1 and somab[0] = 0 exactly (ab_0 = 1 by definition).
+
+    A known pixel is carried at the noise level of the state it is blended into, kn_j = sab[j] known + somab[j] xi: the
+    noise convention of the sampler (:func:`ddim_tables`), not perturb_input's (1 - ab).  ``ab_t`` is the fp32 table of
+    the Schedule; the arithmetic is fp64 numpy, rounded once to fp32, as in ddim_tables.  Pure host function.  Raises
+    ValueError on a non-finite entry (ab_t outside [0, 1])."""
+    if torch.is_tensor(ab_t):
+        ab_t = ab_t.detach().cpu().numpy()
+    ab = np.asarray(ab_t, dtype=np.float32).astype(np.float64).reshape(-1)
+    if ab.size < 2:
+        raise ValueError("ab_t must have T + 1 >= 2 entries")
+    ab[0] = 1.0                                               # ab_0 = 1 by definition
+    with np.errstate(invalid="ignore"):                      # reported below
+        sab, somab = np.sqrt(ab), np.sqrt(1 - ab)
+    if not (np.isfinite(sab).all() and np.isfinite(somab).all()):
+        raise ValueError("the schedule gives non-finite known-region tables (ab_t must lie in [0, 1])")
+    return sab.astype(np.float32), somab.astype(np.float32)
+
+
+KNOWN_NOISE_MODES = ("fixed", "fresh")
+
+
+def check_inpaint(known, mask, n: int, H: int, known_noise: str = "fixed", in_channels: int = 1):
+    """Validate the inputs of masked sampling -> (known [n,1,H,H], mask [n or 1,1,H,H]) as given (any device), or
+    (None, None) when neither is given.  ValueError: an unknown ``known_noise``; one of known / mask without the other;
+    a model with in_channels > 1; a shape other than those; a mask value non-finite or outside [0, 1]; ``known``
+    non-finite where mask > 0 (where the mask is 0 it is never used and may hold anything)."""
+    if known_noise not in KNOWN_NOISE_MODES:
+        raise ValueError(f"known_noise must be one of {KNOWN_NOISE_MODES}, got {known_noise!r}")
+    if known is None and mask is None:
+        return None, None
+    if known is None or mask is None:
+        raise ValueError("masked sampling needs both known= and mask=")
+    if in_channels != 1:
+        raise ValueError("masked sampling is single-channel, like the samplers: the model has in_channels = "
+                         f"{in_channels}")
+    known, mask = torch.as_tensor(known), torch.as_tensor(mask)
+    if tuple(known.shape) != (n, 1, H, H):
+        raise ValueError(f"known must have shape {(n, 1, H, H)}, got {tuple(known.shape)}")
+    if tuple(mask.shape) not in ((n, 1, H, H), (1, 1, H, H)):
+        raise ValueError(f"mask must have shape {(n, 1, H, H)} or {(1, 1, H, H)}, got {tuple(mask.shape)}")
+    if not (known.is_floating_point() and mask.is_floating_point()):
+        raise ValueError("known and mask must be floating-point arrays")
+    if not bool(((mask >= 0) & (mask <= 1)).all()):          # NaN fails both comparisons
+        raise ValueError("mask values must be finite and lie in [0, 1]")
+    if not bool(torch.isfinite(known)[(mask > 0).expand_as(known)].all()):
+        raise ValueError("known holds a non-finite value where mask > 0")
+    return known, mask
+
+
 class GraphSampler:
-    """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed."""
+    """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed.
+
+    Masked (inpainting) sampling, ``inpaint="fixed" | "fresh"`` with ``mask_n`` = n or 1 (the mask's batch extent):
+    ``cdm_mask_blend`` follows the step kernel of every step, in the captured graph and in the eager tail, and
+    re-imposes ``known`` where ``mask`` is 1 at the noise level of the state just written (:func:`known_tables`; the
+    definition is in DESIGN §1).  ``run(x_T, known=, mask=)`` copies the two arrays into buffers allocated here once, so
+    the captured graph serves any contents.  x_T itself is not blended.  The known-region noise xi is one draw for the run
+    ("fixed") or one per step ("fresh"); with z_source="device" it is Philox in a key domain of its own, with "host" it
+    comes from the CPU RNG: "fixed", one randn(n, 1, H, H) before the loop over the steps; "fresh", for i = T..2 one after
+    that step's z and before its shortcut row(s) (the step to i = 0 needs none).  ``inpaint=None`` allocates and
+    launches nothing new."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  save_rate: int = 20, z_source: str = "device", steps_per_graph: int = 10, seed: int = 1234,
-                 snapshots: bool = True, use_graph: bool = True, positions: Optional[int] = None):
+                 snapshots: bool = True, use_graph: bool = True, positions: Optional[int] = None,
+                 inpaint: Optional[str] = None, mask_n: Optional[int] = None):
         """``positions``: the number of steps of a run when it is not T (DDIMSampler); it sizes the per-step tables."""
         from .model import ContextUnet  # noqa: F401
+        if inpaint is not None and inpaint not in KNOWN_NOISE_MODES:
+            raise ValueError(f"inpaint must be None or one of {KNOWN_NOISE_MODES}, got {inpaint!r}")
+        if inpaint is not None and model.in_channels != 1:
+            raise ValueError(f"masked sampling is single-channel: the model has in_channels = {model.in_channels}")
+        mask_n = n if mask_n is None else int(mask_n)
+        if inpaint is not None and mask_n not in (1, n):
+            raise ValueError(f"mask_n must be 1 or n = {n}, got {mask_n}")
+        ktab = known_tables(sched.ab_t) if inpaint is not None else None    # validates before anything is allocated
         self.model, self.sched, self.n = model, sched, n
         self.T = sched.T
         self.npos = self.T if positions is None else int(positions)
@@ -346,9 +422,46 @@ class GraphSampler:
         self.K = max(1, int(steps_per_graph))
         self.use_graph = use_graph
         self.graph = None
+        self.cur_k = self.steps_t = None                     # the strided samplers set them after this constructor
+        self.inpaint = inpaint
+        if inpaint is not None:
+            self.mask_n = mask_n
+            self.known = torch.zeros(n * H * H, device=dev)
+            self.mask = torch.zeros(mask_n * H * H, device=dev)
+            self.ksab, self.ksomab = (torch.from_numpy(v).to(dev) for v in ktab)
+            xi_rows = 1 if inpaint == "fixed" else max(self.npos - 1, 1)
+            self.xi_table = E(xi_rows, n * H * H) if z_source == "host" else None
 
     def _needs_z_table(self):
         return self.z_source == "host"
+
+    def _draw_xi(self, host_z: bool, rows=None):
+        """Host xi of masked sampling: with ``rows`` None the "fixed" draw (before the loop over the steps), else the
+        "fresh" draw of one step, appended to ``rows``.  Nothing is drawn without inpainting or in device mode."""
+        if not host_z or self.inpaint is None:
+            return
+        if self.xi_table is None:
+            raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
+        if rows is None:
+            if self.inpaint == "fixed":
+                self.xi_table.copy_(torch.randn(self.n, 1, self.H, self.H).reshape(1, -1))
+        elif self.inpaint == "fresh":
+            rows.append(torch.randn(self.n, 1, self.H, self.H))
+
+    def _store_xi(self, rows):
+        if rows:
+            self.xi_table.copy_(torch.stack(rows).reshape(len(rows), -1))
+
+    def _blend(self, s):
+        """cdm_mask_blend on the state the step kernel has just written (no-op without inpainting)."""
+        if self.inpaint is None:
+            return
+        numel = self.n * self.H * self.H
+        lib().cdm_mask_blend(_p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(self.known), _p(self.mask),
+                             self.mask.numel(), _p(self.cur_i), _p(self.cur_k), _p(self.steps_t), self.npos, self.T,
+                             _p(self.ksab), _p(self.ksomab), _p(self.xi_table), numel,
+                             1 if self.inpaint == "fresh" else 0, self.seed, _p(self.zseed), _p(self.slot),
+                             _p(self.snaps), s)
 
     # RNG draws in the reference order ------------------------------------------------------------
     def _draw_shortcut_row(self):
@@ -362,15 +475,19 @@ class GraphSampler:
     def prepare_rng(self, host_z: bool):
         """Draw the per-step CPU-RNG quantities (and z in host mode) in reference order."""
         n, H = self.n, self.H
-        rows = []
+        rows, xis = [], []
         zs = [] if host_z else None
+        self._draw_xi(host_z)
         for i in range(self.T, 0, -1):
             if host_z and i > 1:
                 zs.append(torch.randn(n, 1, H, H))
+            if i > 1:
+                self._draw_xi(host_z, xis)
             rows.append(self._draw_shortcut_row())
         self.sc_table.copy_(torch.stack(rows))
         if host_z and zs:
             self.z_table.copy_(torch.stack(zs).reshape(self.T - 1, n * H * H))
+        self._store_xi(xis)
 
     # one step --------------------------------------------------------------------------------------
     def _step(self, s):
@@ -386,6 +503,7 @@ class GraphSampler:
                        1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.sched.coef), _p(self.sched.sa),
                        _p(self.sched.sb), _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
                        _p(self.snaps), self.T, s)
+        self._blend(s)
 
     def _capture(self):
         s = torch.cuda.Stream()
@@ -410,11 +528,18 @@ class GraphSampler:
         if self.use_graph and self.graph is None and self.npos >= self.K:
             self._capture()
 
-    def run(self, x_T: torch.Tensor, steps: Optional[int] = None):
+    def run(self, x_T: torch.Tensor, steps: Optional[int] = None, known=None, mask=None):
         """Run every step (T of them; S for the strided sampler), or the first ``steps``, from x_T [n,1,H,H].
+        A sampler built with ``inpaint`` takes ``known`` [n,1,H,H] and ``mask`` [mask_n,1,H,H] (both required, copied
+        into its buffers; :func:`check_inpaint` is the caller's validation); any other takes neither.
 
         Returns (x [n,1,H,H], intermediate np [slots,n,1,H,H] or None)."""
         n, H = self.n, self.H
+        if (known is None) != (mask is None) or (known is None) != (self.inpaint is None):
+            raise ValueError("known= and mask= go together, with a sampler built with inpaint= and with no other")
+        if known is not None:
+            self.known.copy_(torch.as_tensor(known).to(self.dev, torch.float32).reshape(n * H * H))
+            self.mask.copy_(torch.as_tensor(mask).to(self.dev, torch.float32).reshape(self.mask_n * H * H))
         if self.z_source == "device":
             # fresh z for every run, drawn from torch's CUDA generator (the reference's randn_like(x) on the device
             # consumes it too): reproducible under torch.cuda.manual_seed, different across consecutive calls.
@@ -450,17 +575,22 @@ class DDIMSampler(GraphSampler):
     tau_p the network sees, and ``cdm_ddim_step`` applies x <- (cx[p] x + ce[p] eps) + sigma[p] z.  Snapshots follow
     the reference's rule on positions: ``snapshot_slots(S, save_rate)``.  CPU-RNG order (z_source="host"), for
     p = S..1: z (only when eta > 0 and p > 1), then the shortcut row(s), cond before uncond; eta = 0 draws no z at all.
-    In "device" mode z is Philox stream tau_p of the per-run key, as the full sampler's stream i."""
+    In "device" mode z is Philox stream tau_p of the per-run key, as the full sampler's stream i.
+
+    Masked sampling (``inpaint``, ``mask_n``: see :class:`GraphSampler`) blends after every position, at the noise level
+    of tau_{p-1}.  Host xi: "fixed", one randn(n, 1, H, H) before the loop over the positions; "fresh", for p = S..2 one
+    after that position's z (if any) and before its shortcut row(s)."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  steps=50, eta: float = 0.0, spacing="uniform", save_rate: int = 20, z_source: str = "device",
-                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True):
+                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
+                 inpaint: Optional[str] = None, mask_n: Optional[int] = None):
         self.taus = timestep_subsequence(sched.T, steps, spacing)
         self.S = len(self.taus)
         self.eta = float(eta)
         cx, ce, sg = ddim_tables(sched.ab_t, self.taus, self.eta)          # validates eta before anything is allocated
         super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, positions=self.S)
+                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
         dev = self.dev
         self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
         self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(dev) for v in (cx, ce, sg))
@@ -471,16 +601,20 @@ class DDIMSampler(GraphSampler):
 
     def prepare_rng(self, host_z: bool):
         n, H = self.n, self.H
-        rows, zs = [], []
+        rows, zs, xis = [], [], []
+        self._draw_xi(host_z)
         for p in range(self.S, 0, -1):
             if host_z and self.eta > 0 and p > 1:
                 zs.append(torch.randn(n, 1, H, H))
+            if p > 1:
+                self._draw_xi(host_z, xis)
             rows.append(self._draw_shortcut_row())
         self.sc_table.copy_(torch.stack(rows))
         if zs:
             if self.z_table is None:
                 raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
             self.z_table.copy_(torch.stack(zs).reshape(self.S - 1, n * H * H))
+        self._store_xi(xis)
 
     def _step(self, s):
         lb = lib()
@@ -495,6 +629,7 @@ class DDIMSampler(GraphSampler):
                          1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.cur_k), _p(self.cx), _p(self.ce),
                          _p(self.sigma), self.S, _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
                          _p(self.snaps), s)
+        self._blend(s)
 
 
 class DPMSolverSampler(GraphSampler):
@@ -505,17 +640,25 @@ class DPMSolverSampler(GraphSampler):
     timestep; ``cdm_dpmpp_step`` applies the update and keeps the previous data prediction in ``dprev``, allocated here
     once so a captured graph stays valid across runs (its stale contents are never read: c1 = 0 at the first position).
     The solver is deterministic: no z in any ``z_source``.  CPU-RNG order, for p = S..1: the shortcut row(s), cond
-    before uncond, and nothing else.  Snapshots: ``snapshot_slots(S, save_rate)`` on positions."""
+    before uncond, and nothing else.  Snapshots: ``snapshot_slots(S, save_rate)`` on positions.
+
+    Masked sampling (``inpaint``, ``mask_n``: see :class:`GraphSampler`) blends after every position, at the noise level
+    of tau_{p-1}; ``dprev`` keeps the data prediction computed before the blend (from the state the network saw), the
+    blended state enters the next position as x_i.  Use "fixed": noise re-drawn at every step ("fresh") breaks the
+    smoothness along the trajectory that the second-order combination relies on.  The known-region xi is the one
+    quantity that depends on ``z_source`` here.  Host xi: "fixed", one randn(n, 1, H, H) before the loop over the
+    positions; "fresh", for p = S..2 one before that position's shortcut row(s)."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  steps=20, order: int = 2, spacing="uniform", save_rate: int = 20, z_source: str = "device",
-                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True):
+                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
+                 inpaint: Optional[str] = None, mask_n: Optional[int] = None):
         self.taus = timestep_subsequence(sched.T, steps, spacing)
         self.S = len(self.taus)
         tables = dpmpp_tables(sched.ab_t, self.taus, order)               # validates order before anything is allocated
         self.order = int(order)
         super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, positions=self.S)
+                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
         dev = self.dev
         self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
         self.tables = tuple(torch.from_numpy(v).to(dev) for v in tables)  # sq, ra, c0, c1, cx, cd
@@ -526,7 +669,14 @@ class DPMSolverSampler(GraphSampler):
         return False
 
     def prepare_rng(self, host_z: bool):
-        self.sc_table.copy_(torch.stack([self._draw_shortcut_row() for _ in range(self.S)]))
+        rows, xis = [], []
+        self._draw_xi(host_z)
+        for p in range(self.S, 0, -1):
+            if p > 1:
+                self._draw_xi(host_z, xis)
+            rows.append(self._draw_shortcut_row())
+        self.sc_table.copy_(torch.stack(rows))
+        self._store_xi(xis)
 
     def _step(self, s):
         lb = lib()
@@ -540,6 +690,7 @@ class DPMSolverSampler(GraphSampler):
         lb.cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
                           1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.S,
                           _p(self.dprev), _p(self.slot), _p(self.snaps), s)
+        self._blend(s)
 
 
 class DDPM:
@@ -563,9 +714,11 @@ class DDPM:
     def denoise_add_noise(self, x, t, pred_noise, z=None):
         return denoise_add_noise(x, t, pred_noise, z, self.sched)
 
-    def _sampler(self, n, guide_w, params, save_rate, ddim=None, dpm=None):
+    def _sampler(self, n, guide_w, params, save_rate, ddim=None, dpm=None, inpaint=None):
         """The cached sampler of a configuration; ``ddim = (steps, eta, spacing)`` selects the strided one,
-        ``dpm = (steps, order, spacing)`` the multistep one (its key starts with a tag no DDIM key holds)."""
+        ``dpm = (steps, order, spacing)`` the multistep one (its key starts with a tag no DDIM key holds);
+        ``inpaint = (known_noise, mask batch extent)`` the masked form of any of them (a trailing tagged entry of the
+        key: the contents of known / mask are not part of it, one sampler and one captured graph serve them all)."""
         key = (n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, self.z_source)
         if ddim is not None:
             steps, eta, spacing = ddim
@@ -573,115 +726,160 @@ class DDPM:
         elif dpm is not None:
             steps, order, spacing = dpm
             key += ("dpmpp", steps, order, spacing if isinstance(spacing, str) else tuple(spacing))
+        ip = {}
+        if inpaint is not None:
+            key += (("inpaint",) + tuple(inpaint),)
+            ip = dict(inpaint=inpaint[0], mask_n=inpaint[1])
         smp = self._samplers.get(key)
         if smp is None and ddim is not None:
             smp = self._samplers[key] = DDIMSampler(self.model, self.sched, n, guide_w, params, steps, eta, spacing,
-                                                    save_rate, self.z_source, seed=self.seed)
+                                                    save_rate, self.z_source, seed=self.seed, **ip)
         elif smp is None and dpm is not None:
             smp = self._samplers[key] = DPMSolverSampler(self.model, self.sched, n, guide_w, params, steps, order,
-                                                         spacing, save_rate, self.z_source, seed=self.seed)
+                                                         spacing, save_rate, self.z_source, seed=self.seed, **ip)
         elif smp is None:
             smp = self._samplers[key] = GraphSampler(self.model, self.sched, n, guide_w, params, save_rate,
-                                                     self.z_source, seed=self.seed)
+                                                     self.z_source, seed=self.seed, **ip)
         elif params is not None:
             smp.cbuf[:n] = params.to(smp.dev, torch.float32).reshape(n, -1)
         return smp
 
+    def _inpaint_args(self, known, mask, known_noise, n):
+        """Validated masked-sampling inputs -> (the ``inpaint`` entry of :meth:`_sampler`, run() keywords); (None, {})
+        without them.  Called before anything is drawn, so a ValueError leaves the CPU RNG where it was."""
+        known, mask = check_inpaint(known, mask, n, self.model.h, known_noise, self.model.in_channels)
+        if known is None:
+            return None, {}
+        return (known_noise, int(mask.shape[0])), dict(known=known, mask=mask)
+
     @torch.no_grad()
-    def sample_ddpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, save_rate=20):
-        """code/train_diffusion_condition.py:281-335 -> (samples, intermediate)."""
+    def sample_ddpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, save_rate=20, *, known=None,
+                    mask=None, known_noise="fixed"):
+        """code/train_diffusion_condition.py:281-335 -> (samples, intermediate).  ``known`` [n,1,size,size] and ``mask``
+        [n or 1,1,size,size] (keyword only, both or neither; 1 = known pixel, 0 = generated, between: a soft blend) run
+        masked sampling with the known-region noise mode ``known_noise`` ("fixed" | "fresh", :class:`GraphSampler`);
+        :func:`check_inpaint` lists what raises ValueError."""
         assert size == self.model.h
+        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
         host = self.z_source == "host"
         x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as the reference
         if params is None:
             params = torch.rand(n_sample, self.n_cfeat)      # CPU RNG, as the reference
-        smp = self._sampler(n_sample, guide_w, params, save_rate)
+        smp = self._sampler(n_sample, guide_w, params, save_rate, inpaint=ip)
         smp.prepare_rng(host_z=host)
-        return smp.run(x_T)
+        return smp.run(x_T, **kw)
 
     @torch.no_grad()
-    def sample_ddpm_from_noise(self, noise_images, params=None, save_rate=20, guide_w=0.0):
-        """code/train_diffusion_condition.py:337-384 (and the unconditional code/train_diffusion.py:170-193)."""
+    def sample_ddpm_from_noise(self, noise_images, params=None, save_rate=20, guide_w=0.0, *, known=None, mask=None,
+                               known_noise="fixed"):
+        """code/train_diffusion_condition.py:337-384 (and the unconditional code/train_diffusion.py:170-193).
+        ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm` (noise_images is not blended)."""
         n = noise_images.shape[0]
-        smp = self._sampler(n, guide_w, params, save_rate)
+        ip, kw = self._inpaint_args(known, mask, known_noise, n)
+        smp = self._sampler(n, guide_w, params, save_rate, inpaint=ip)
         smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images)
-
+        return smp.run(noise_images, **kw)
 
     @torch.no_grad()
     def sample_ddim(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=50, eta=0.0,
-                    spacing="uniform", save_rate=20):
+                    spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm on ``steps`` of the T timesteps (:class:`DDIMSampler`; ``spacing``: "uniform", "quadratic" or an
         explicit increasing timestep list ending at T, then ``steps`` may be None) -> (samples, intermediate).  x_T and
         random params consume the CPU RNG as sample_ddpm does; eta = 0 is deterministic given x_T and the shortcut
-        draws, eta = 1 has the ancestral sampler's variance.  Snapshots: snapshot_slots(steps, save_rate) on positions."""
+        draws, eta = 1 has the ancestral sampler's variance.  Snapshots: snapshot_slots(steps, save_rate) on positions.
+        ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm`."""
         assert size == self.model.h
+        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
         x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
         if params is None:
             params = torch.rand(n_sample, self.n_cfeat)
-        smp = self._sampler(n_sample, guide_w, params, save_rate, (steps, eta, spacing))
+        smp = self._sampler(n_sample, guide_w, params, save_rate, (steps, eta, spacing), inpaint=ip)
         smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(x_T)
+        return smp.run(x_T, **kw)
 
     @torch.no_grad()
     def sample_ddim_from_noise(self, noise_images, params=None, steps=50, eta=0.0, spacing="uniform", save_rate=20,
-                               guide_w=0.0):
+                               guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_ddim`)."""
         n = noise_images.shape[0]
-        smp = self._sampler(n, guide_w, params, save_rate, (steps, eta, spacing))
+        ip, kw = self._inpaint_args(known, mask, known_noise, n)
+        smp = self._sampler(n, guide_w, params, save_rate, (steps, eta, spacing), inpaint=ip)
         smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images)
+        return smp.run(noise_images, **kw)
 
     @torch.no_grad()
     def sample_dpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=20, order=2,
-                   spacing="uniform", save_rate=20):
+                   spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm on ``steps`` of the T timesteps with the second-order multistep update (:class:`DPMSolverSampler`;
         ``order=1``: first order throughout; ``spacing`` as in :meth:`sample_ddim`) -> (samples, intermediate).  x_T and
         random params consume the CPU RNG as sample_ddpm does; the run is deterministic given x_T and the shortcut
-        draws.  Snapshots: snapshot_slots(steps, save_rate) on positions."""
+        draws.  Snapshots: snapshot_slots(steps, save_rate) on positions.  ``known`` / ``mask`` / ``known_noise``:
+        masked sampling, as in :meth:`sample_ddpm` (keep "fixed" here, see :class:`DPMSolverSampler`)."""
         assert size == self.model.h
+        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
         x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
         if params is None:
             params = torch.rand(n_sample, self.n_cfeat)
-        smp = self._sampler(n_sample, guide_w, params, save_rate, dpm=(steps, order, spacing))
+        smp = self._sampler(n_sample, guide_w, params, save_rate, dpm=(steps, order, spacing), inpaint=ip)
         smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(x_T)
+        return smp.run(x_T, **kw)
 
     @torch.no_grad()
     def sample_dpm_from_noise(self, noise_images, params=None, steps=20, order=2, spacing="uniform", save_rate=20,
-                              guide_w=0.0):
+                              guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_dpm`)."""
         n = noise_images.shape[0]
-        smp = self._sampler(n, guide_w, params, save_rate, dpm=(steps, order, spacing))
+        ip, kw = self._inpaint_args(known, mask, known_noise, n)
+        smp = self._sampler(n, guide_w, params, save_rate, dpm=(steps, order, spacing), inpaint=ip)
         smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images)
+        return smp.run(noise_images, **kw)
+
+    def inpaint(self, known, mask, params=None, guide_w=0.0, sampler="ddpm", **sampler_kwargs):
+        """Complete the maps ``known`` [n,1,H,H] where ``mask`` [n or 1,1,H,H] is 0 -> (samples, intermediate).
+
+        ``sampler``: "ddpm" (:meth:`sample_ddpm`), "ddim" (:meth:`sample_ddim`) or "dpmpp" (:meth:`sample_dpm`); x_T and
+        random params are drawn as that method draws them, and ``sampler_kwargs`` are its keywords (steps, eta, order,
+        spacing, save_rate, known_noise)."""
+        fns = {"ddpm": self.sample_ddpm, "ddim": self.sample_ddim, "dpmpp": self.sample_dpm}
+        if sampler not in fns:
+            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', got {sampler!r}")
+        if known is None or mask is None:
+            raise ValueError("masked sampling needs both known and mask")
+        known = torch.as_tensor(known)
+        if known.dim() != 4:
+            raise ValueError(f"known must have shape [n, 1, H, H], got {tuple(known.shape)}")
+        return fns[sampler](known.shape[0], self.model.h, None, params, guide_w, known=known, mask=mask,
+                            **sampler_kwargs)
 
 
 @torch.no_grad()
 def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.0, timesteps=1000, b_t=None,
                 a_t=None, ab_t=None, z_source="device", *, steps=None, eta=0.0, spacing="uniform", solver="ddim",
-                order=2):
+                order=2, known=None, mask=None, known_noise="fixed"):
     """Functional sampler of code/sample_power_spectra.py:71-110 (returns the final x only).  b_t / a_t / ab_t are
     the caller's schedule, as in the reference (all three or none: None builds the default schedule).
     ``steps`` (keyword only; None: the reference's T-step ancestral sampler) runs DDPM.sample_ddim with ``eta`` and
     ``spacing`` on that many of the timesteps, or, with ``solver="dpmpp"``, DDPM.sample_dpm with ``order`` and ``spacing``
-    (``solver`` is only consulted when ``steps`` is given)."""
+    (``solver`` is only consulted when ``steps`` is given).  ``known`` / ``mask`` / ``known_noise`` (keyword only): masked
+    sampling with whichever of the three is selected, as in DDPM.sample_ddpm."""
     given = [v is not None for v in (b_t, a_t, ab_t)]
     if any(given) and not all(given):
         raise ValueError("pass all of b_t, a_t, ab_t or none of them")
     d = DDPM(model, timesteps, device or model.out[3].weight.device, z_source=z_source,
              sched_tensors=(b_t, a_t, ab_t) if all(given) else None)
+    ipk = dict(known=known, mask=mask, known_noise=known_noise)
     if steps is not None:
         if solver == "dpmpp":
-            return d.sample_dpm(n_sample, size, device, params, guide_w, steps, order, spacing)[0]
+            return d.sample_dpm(n_sample, size, device, params, guide_w, steps, order, spacing, **ipk)[0]
         if solver != "ddim":
             raise ValueError(f"solver must be 'ddim' or 'dpmpp', got {solver!r}")
-        return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing)[0]
+        return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing, **ipk)[0]
     if params is None:
+        ip, kw = d._inpaint_args(known, mask, known_noise, n_sample)
         x_T = torch.randn(n_sample, 1, size, size)
         params = torch.rand(n_sample, 6 if model.n_cfeat == 6 else model.n_cfeat)
-        smp = d._sampler(n_sample, guide_w, params, 20)
+        smp = d._sampler(n_sample, guide_w, params, 20, inpaint=ip)
         smp.prepare_rng(host_z=z_source == "host")
-        return smp.run(x_T)[0]
-    x, _ = d.sample_ddpm(n_sample, size, device, params, guide_w)
+        return smp.run(x_T, **kw)[0]
+    x, _ = d.sample_ddpm(n_sample, size, device, params, guide_w, **ipk)
     return x

@@ -40,6 +40,10 @@ Training for guided sampling (all off by default; without them the outputs are t
   --sample-steps S --sampler dpmpp [--solver-order 1|2] [--spacing ...]
                  the same S timesteps with the second-order multistep solver (DPM-Solver++ 2M, deterministic; order 1
                  is its first-order form); the log lines then name steps=S, dpmpp order=O.  Not with a non-zero --eta.
+  --inpaint-known PATH.npy --inpaint-mask PATH.npy [--inpaint-noise fixed|fresh]
+                 after the sampling above, complete the --n-samples maps of the first file where the mask of the second
+                 is 0 (masked sampling with the sampler the flags above select; arrays [n,H,W] or [n,1,H,W], the mask
+                 also [H,W]; 1 = keep the pixel) and write inpainted_samples.npy; the log gets an "Inpainting" line.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -59,6 +63,28 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cdm_amd.data import preprocess_maps, preprocess_params, train_test_split  # noqa: E402
+
+
+def load_inpaint(known_path, mask_path, n, H):
+    """The --inpaint-known / --inpaint-mask files as fp32 tensors (known [n,1,H,H], mask [n or 1,1,H,H]).  ValueError
+    for a shape other than [n,H,H] / [n,1,H,H] (the mask also [H,H]) and for what cdm_amd.check_inpaint rejects."""
+    from cdm_amd.diffusion import check_inpaint
+    known, mask = (np.load(p, allow_pickle=False) for p in (known_path, mask_path))
+    if mask.ndim == 2:
+        mask = mask[None]
+    out = []
+    for name, v in (("known", known), ("mask", mask)):
+        if v.ndim == 4 and v.shape[1] == 1:
+            v = v[:, 0]
+        if v.ndim != 3 or v.shape[1:] != (H, H):
+            raise ValueError(f"{name} has shape {v.shape}: expected [n, {H}, {H}] or [n, 1, {H}, {H}]")
+        if not (np.issubdtype(v.dtype, np.floating) or np.issubdtype(v.dtype, np.integer) or v.dtype == np.bool_):
+            raise ValueError(f"{name} has dtype {v.dtype}: expected numbers")
+        out.append(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))[:, None])
+    known, mask = out
+    if known.shape[0] != n:
+        raise ValueError(f"known holds {known.shape[0]} maps, --n-samples is {n}")
+    return check_inpaint(known, mask, n, H)
 
 
 def main(argv=None):
@@ -92,7 +118,21 @@ def main(argv=None):
     ap.add_argument("--sampler", choices=["ddim", "dpmpp"], default="ddim",
                     help="the update --sample-steps uses: strided DDIM, or the multistep DPM-Solver++ (2M)")
     ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="order of --sampler dpmpp")
+    ap.add_argument("--inpaint-known", default=None, metavar="PATH.npy",
+                    help="maps [n,H,W] or [n,1,H,W] (normalised data units) whose masked pixels are kept; n = --n-samples")
+    ap.add_argument("--inpaint-mask", default=None, metavar="PATH.npy",
+                    help="mask [n,H,W], [n,1,H,W] or [H,W] in [0, 1]: 1 = keep the pixel of --inpaint-known, 0 = generate")
+    ap.add_argument("--inpaint-noise", choices=["fixed", "fresh"], default="fixed",
+                    help="known-region noise: one draw for the run, or one per step")
     a = ap.parse_args(argv)
+    if (a.inpaint_known is None) != (a.inpaint_mask is None):
+        ap.error("--inpaint-known and --inpaint-mask go together")
+    a.inpaint = None
+    if a.inpaint_known is not None:
+        try:
+            a.inpaint = load_inpaint(a.inpaint_known, a.inpaint_mask, a.n_samples, a.height)
+        except (OSError, ValueError) as e:
+            ap.error(f"--inpaint-known / --inpaint-mask: {e}")
     if a.sample_steps < 0 or a.sample_steps > a.timesteps:
         ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
     if a.clip_grad is not None and not a.clip_grad > 0:
@@ -281,6 +321,22 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
         dt = time.time() - t0
         np.save(os.path.join(out_dir, "generated_samples.npy"), samples.cpu().numpy())
         log.write(f"Sampling {ns} maps (w={a.guide_w}), {how}: {dt:.2f} s ({ns / dt:.3f} img/s)\n")
+    if a.inpaint is not None:
+        known, mask = a.inpaint
+        ipk = dict(known=known, mask=mask, known_noise=a.inpaint_noise)
+        x_T = torch.randn(ns, 1, H, H)                       # CPU RNG, as the sample_* methods draw it
+        t0 = time.time()
+        if dpm:
+            filled, _ = d.sample_dpm_from_noise(x_T, p, guide_w=a.guide_w, **dpm, **ipk)
+        elif ddim:
+            filled, _ = d.sample_ddim_from_noise(x_T, p, guide_w=a.guide_w, **ddim, **ipk)
+        else:
+            filled, _ = d.sample_ddpm_from_noise(x_T, p, guide_w=a.guide_w, **ipk)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        np.save(os.path.join(out_dir, "inpainted_samples.npy"), filled.cpu().numpy())
+        log.write(f"Inpainting {ns} maps (w={a.guide_w}, {float(mask.mean()):.3f} of the pixels known, "
+                  f"{a.inpaint_noise} noise), {how}: {dt:.2f} s\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

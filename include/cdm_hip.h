@@ -428,6 +428,23 @@ int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long numel, const
                    const int* cur_k, const float* sq, const float* ra, const float* c0, const float* c1,
                    const float* cx, const float* cd, int npos, float* dprev, const int* snap_slot, float* snaps,
                    void* stream);
+/* masked (inpainting) sampling: re-impose the known pixels on the state a step kernel (cdm_denoise, cdm_ddim_step,
+ * cdm_dpmpp_step) has just written.  The step went from the timestep i = *cur_i to j: cur_k or steps null is the
+ * ancestral form, position i of 1..T and j = i - 1; otherwise position k = *cur_k of 1..npos and j = steps[k - 1].
+ * With separate fp32 roundings (m = mask[e % mask_numel], so a mask of numel / batch elements serves every sample):
+ *   kn = sab[j] known + somab[j] xi  (j >= 1);  kn = known  (j == 0: xi neither read nor drawn, no multiply)
+ *   x  = m kn + (1 - m) x            (m == 1 stores kn, m == 0 keeps x, bit for bit; known is not read where m == 0)
+ * sab / somab [T + 1]: sqrt(ab) and sqrt(1 - ab) by timestep (diffusion.known_tables).  xi = row (fresh ? rows -
+ * position : 0) of xi_table (rows = T or npos: the row order of the z tables) at stride xistride when given, else
+ * Philox keyed by (seed ^ *seed_dev) ^ a fixed constant (a stream domain disjoint from z's), stream (fresh ? j : 0).
+ * Writes x (and both halves of x2 when given; x2 may alias x) and the snapshot slot snap_slot[position] of snaps when
+ * >= 0.  A position outside its range, or i outside 1..T, writes nothing.  hipErrorInvalidValue, nothing launched:
+ * numel <= 0, mask_numel <= 0, numel % mask_numel != 0, a required pointer null, T < 1, npos outside 1..T in the strided
+ * form, xistride < 0, snap_slot without snaps. */
+int cdm_mask_blend(float* x, float* x2, long long numel, const float* known, const float* mask, long long mask_numel,
+                   const int* cur_i, const int* cur_k, const int* steps, int npos, int T, const float* sab,
+                   const float* somab, const float* xi_table, long long xistride, int fresh, unsigned long long seed,
+                   const long long* seed_dev, const int* snap_slot, float* snaps, void* stream);
 /* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
