@@ -948,20 +948,51 @@ __global__ void mse_finalize_kernel(const float* partial, int nb, double inv_num
     if (nonfinite && !isfinite(loss)) *nonfinite += 1;
 }
 
-// Sampler step prologue (device-side step counter, so one captured step replays for every i):
-//   i = *ctr; *ctr = i - 1; cur[0] = i; t_cur = (float)((double)i / T); shortcut rows for step i.
-__global__ void sample_prologue_kernel(int* ctr, int T, int* cur_i, float* t_cur, const float* sc_table, int sc_row,
-                                       float* sc_cur) {
-    const int i = *ctr;
+// Sampler step prologue (device-side step counter, so one captured step replays for every position).  The counter
+// holds the position k = S..1 of a run of S steps:
+//   k = *ctr; *ctr = k - 1; cur_k = k; cur_i = i; t_cur = (float)((double)i / T); shortcut row S - k.
+// steps null is the ancestral form: S = T and the position is the timestep, i = k (cur_k may then be null too).
+// Otherwise i = steps[k] of the timestep subsequence steps[0..S] (steps[0] = 0, steps[S] = T).
+// A counter outside 1..S (a replay past the last position) writes and reads nothing.
+__global__ void sample_prologue_kernel(int* ctr, int S, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
+                                       const float* sc_table, int sc_row, float* sc_cur) {
+    const int k = *ctr;
     __syncthreads();
-    if (threadIdx.x == 0) { *ctr = i - 1; *cur_i = i; *t_cur = (float)((double)i / (double)T); }
+    if (k < 1 || k > S) return;
+    if (threadIdx.x == 0) {
+        const int i = steps ? steps[k] : k;
+        *ctr = k - 1; *cur_i = i; *t_cur = (float)((double)i / (double)T);
+        if (cur_k) *cur_k = k;
+    }
     if (sc_table)
-        for (int k = threadIdx.x; k < sc_row; k += blockDim.x) sc_cur[k] = sc_table[(long long)(T - i) * sc_row + k];
+        for (int q = threadIdx.x; q < sc_row; q += blockDim.x) sc_cur[q] = sc_table[(long long)(S - k) * sc_row + q];
 }
 
-// x <- (x - eps*coef[i]) / sa[i] + sb[i]*z ;  eps = eu + w (ec - eu) when cfg (model batch = 2n)
-// z = 0 at i == 1; z from z_table[(T-i)][e] when given, else Philox(seed, stream i).
-// Writes x into both halves of the model-input buffer (x2 may alias x), and a snapshot when slot[i] >= 0.
+// The pieces the kernels that write the sampler state share; the arithmetic of each update stays in its kernel.
+// eps of a step: eu + w (ec - eu) when cfg (classifier-free guidance; model batch = 2n, cond half first), else eps[e].
+static __device__ __forceinline__ float cfg_eps(const float* eps, long long numel, long long e, int cfg, float w) {
+#pragma clang fp contract(off)  // per function, so needed here too: a fused w * (ep - eu) + eu is another rounding
+    const float ep = eps[e];
+    if (!cfg) return ep;
+    const float eu = eps[numel + e];
+    return eu + w * (ep - eu);
+}
+// per-run Philox key: seed ^ *seed_dev (drawn from torch's CUDA generator before every run, so consecutive sampling
+// calls get fresh z, as the reference's randn_like on the device does)
+static __device__ __forceinline__ unsigned long long run_key(unsigned long long seed, const long long* seed_dev) {
+    return seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed;
+}
+// Writes v into x and both halves of the model-input buffer (x2 may alias x), and a snapshot when slot >= 0.
+static __device__ __forceinline__ void store_state(float v, long long e, long long numel, float* x, float* x2, int slot,
+                                                   float* snaps) {
+    x[e] = v;
+    if (x2) { x2[e] = v; x2[numel + e] = v; }
+    if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+}
+
+// x <- (x - eps*coef[i]) / sa[i] + sb[i]*z ;  eps: cfg_eps
+// z = 0 at i == 1; z from z_table[(T-i)][e] when given, else Philox(run_key, stream i).
+// Write-out: store_state, slot[i].
 __global__ void denoise_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
                                float w, const int* cur_i, const float* coef, const float* sa, const float* sb,
                                const float* z_table, long long zstride, unsigned long long seed,
@@ -970,44 +1001,21 @@ __global__ void denoise_kernel(const float* xin, float* x, float* x2, long long 
     const int i = *cur_i;
     const float cf = coef[i], a = sa[i], b = sb[i];
     const int slot = snap_slot ? snap_slot[i] : -1;
-    // per-run key: seed ^ *seed_dev (drawn from torch's CUDA generator before every run, so consecutive sampling
-    // calls get fresh z, as the reference's randn_like on the device does)
-    const unsigned long long sd = seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed;
+    const unsigned long long sd = run_key(seed, seed_dev);
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
-        float ep = eps[e];
-        if (cfg) { const float eu = eps[numel + e]; ep = eu + w * (ep - eu); }
+        const float ep = cfg_eps(eps, numel, e, cfg, w);
         float z = 0.f;
         if (i > 1) z = z_table ? z_table[(long long)(T - i) * zstride + e] : philox_normal(sd, (uint32_t)i, e);
         const float mean = (xin[e] - ep * cf) / a;   // same op order / roundings as the reference
-        const float v = mean + b * z;
-        x[e] = v;
-        if (x2) { x2[e] = v; x2[numel + e] = v; }
-        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+        store_state(mean + b * z, e, numel, x, x2, slot, snaps);
     }
-}
-
-// Strided (DDIM) sampler prologue: the device counter holds the position k = S..1 in the timestep subsequence
-// steps[0..S] (steps[0] = 0, steps[S] = T):
-//   k = *ctr; *ctr = k - 1; cur_k = k; cur_i = i = steps[k]; t_cur = (float)((double)i / T); shortcut row S - k.
-// A counter outside 1..S (a replay past the last position) writes nothing.
-__global__ void sample_prologue_sub_kernel(int* ctr, int S, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
-                                           const float* sc_table, int sc_row, float* sc_cur) {
-    const int k = *ctr;
-    __syncthreads();
-    if (k < 1 || k > S) return;
-    if (threadIdx.x == 0) {
-        const int i = steps[k];
-        *ctr = k - 1; *cur_i = i; *cur_k = k; *t_cur = (float)((double)i / (double)T);
-    }
-    if (sc_table)
-        for (int q = threadIdx.x; q < sc_row; q += blockDim.x) sc_cur[q] = sc_table[(long long)(S - k) * sc_row + q];
 }
 
 // Strided update from i = steps[k] to j = steps[k-1] (generalised DDIM, noise predicted with sqrt(1 - ab) as in
-// denoise_kernel): x <- (cx[k]*x + ce[k]*eps) + sigma[k]*z ;  eps = eu + w (ec - eu) when cfg (model batch = 2n).
+// denoise_kernel): x <- (cx[k]*x + ce[k]*eps) + sigma[k]*z ;  eps: cfg_eps.
 // cx / ce / sigma [S+1]: host tables (diffusion.ddim_tables).  z is neither read nor drawn when sigma[k] == 0 (eta = 0,
-// and the last position); else z_table[(S-k)][e] when given, else Philox(seed, stream i) keyed by the timestep.
-// Writes x into both halves of the model-input buffer (x2 may alias x), and a snapshot when slot[k] >= 0.
+// and the last position); else z_table[(S-k)][e] when given, else Philox(run_key, stream i) keyed by the timestep.
+// Write-out: store_state, slot[k].  A k outside 1..S writes nothing.
 __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
                                  float w, const int* cur_i, const int* cur_k, const float* cx, const float* ce,
                                  const float* sigma, int S, const float* z_table, long long zstride,
@@ -1017,27 +1025,22 @@ __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long lon
     if (k < 1 || k > S) return;
     const float a = cx[k], c = ce[k], sg = sigma[k];
     const int slot = snap_slot ? snap_slot[k] : -1;
-    const unsigned long long sd = seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed;
+    const unsigned long long sd = run_key(seed, seed_dev);
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
-        float ep = eps[e];
-        if (cfg) { const float eu = eps[numel + e]; ep = eu + w * (ep - eu); }
-        float v = a * xin[e] + c * ep;
+        float v = a * xin[e] + c * cfg_eps(eps, numel, e, cfg, w);
         if (sg != 0.f) {
             const float z = z_table ? z_table[(long long)(S - k) * zstride + e] : philox_normal(sd, (uint32_t)i, e);
             v = v + sg * z;
         }
-        x[e] = v;
-        if (x2) { x2[e] = v; x2[numel + e] = v; }
-        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+        store_state(v, e, numel, x, x2, slot, snaps);
     }
 }
 
 // Second-order multistep update (DPM-Solver++ 2M) from i = steps[k] to j = steps[k-1], on the data prediction:
 //   d = (x - sq[k]*eps) * ra[k];  D = d when c1[k] == 0, else c0[k]*d + c1[k]*dprev;  x <- cx[k]*x + cd[k]*D;  dprev <- d
-// eps = eu + w (ec - eu) when cfg (model batch = 2n).  sq / ra / c0 / c1 / cx / cd [S+1]: host tables
-// (diffusion.dpmpp_tables).  dprev is not read where c1[k] == 0 (the first position, where it is uninitialised or stale
-// from an earlier run, the last, and every position at order 1): 0 * NaN must not reach x.  No z: the solver is
-// deterministic.  Writes x into both halves of the model-input buffer (x2 may alias x), and a snapshot when slot[k] >= 0.
+// eps: cfg_eps.  sq / ra / c0 / c1 / cx / cd [S+1]: host tables (diffusion.dpmpp_tables).  dprev is not read where
+// c1[k] == 0 (the first position, where it is uninitialised or stale from an earlier run, the last, and every position at
+// order 1): 0 * NaN must not reach x.  No z: the solver is deterministic.  Write-out: store_state, slot[k].
 __global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
                                   float w, const int* cur_k, const float* sq, const float* ra, const float* c0,
                                   const float* c1, const float* cx, const float* cd, int S, float* dprev,
@@ -1048,17 +1051,14 @@ __global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long lo
     const float s = sq[k], r = ra[k], a0 = c0[k], a1 = c1[k], a = cx[k], c = cd[k];
     const int slot = snap_slot ? snap_slot[k] : -1;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
-        float ep = eps[e];
-        if (cfg) { const float eu = eps[numel + e]; ep = eu + w * (ep - eu); }
+        const float ep = cfg_eps(eps, numel, e, cfg, w);
         const float xe = xin[e];
         const float d = (xe - s * ep) * r;
         float D = d;
         if (a1 != 0.f) D = a0 * d + a1 * dprev[e];
         const float v = a * xe + c * D;
         dprev[e] = d;
-        x[e] = v;
-        if (x2) { x2[e] = v; x2[numel + e] = v; }
-        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+        store_state(v, e, numel, x, x2, slot, snaps);
     }
 }
 
@@ -1069,12 +1069,12 @@ __global__ void dpmpp_step_kernel(const float* xin, float* x, float* x2, long lo
 //   x  = m*kn + (1 - m)*x             each product and the sum its own fp32 rounding; m == 1 stores kn and m == 0 keeps x
 //                                     as they are (no 0 * inf, no signed-zero change: bit for bit; xi is not needed at m == 0)
 // m = mask[e % mask_numel] (a [1,1,H,W] mask serves the whole batch).  xi: row (fresh ? rows - position : 0) of xi_table
-// (rows = T or npos, the row order of the z tables) when given, else Philox keyed by (seed ^ *seed_dev) ^
-// KNOWN_NOISE_DOMAIN, stream (fresh ? j : 0).  The XOR moves the known-region noise to a key no z draw of the run uses
-// (z: key seed ^ *seed_dev, streams 1..T), so xi is independent of every z whatever the streams are; the constant is the
-// ASCII of "known_xi" and has no other meaning.
-// Writes x, both halves of the model-input buffer (x2 may alias x) and the snapshot slot of this position when >= 0 (the
-// step kernel stored the unblended state there).  A position outside its range, or i outside 1..T, writes nothing.
+// (rows = T or npos, the row order of the z tables) when given, else Philox keyed by run_key ^ KNOWN_NOISE_DOMAIN,
+// stream (fresh ? j : 0).  The XOR moves the known-region noise to a key no z draw of the run uses (z: key run_key,
+// streams 1..T), so xi is independent of every z whatever the streams are; the constant is the ASCII of "known_xi" and
+// has no other meaning.
+// Write-out: store_state, the slot of this position (the step kernel stored the unblended state there).  A position
+// outside its range, or i outside 1..T, writes nothing.
 constexpr unsigned long long KNOWN_NOISE_DOMAIN = 0x6B6E6F776E5F7869ull;
 __global__ void mask_blend_kernel(float* x, float* x2, long long numel, const float* known, const float* mask,
                                   long long mask_numel, const int* cur_i, const int* cur_k, const int* steps, int npos,
@@ -1094,7 +1094,7 @@ __global__ void mask_blend_kernel(float* x, float* x2, long long numel, const fl
     const int slot = snap_slot ? snap_slot[pos] : -1;
     const float sa = sab[j], so = somab[j];
     const float* xr = xi_table ? xi_table + (fresh ? (long long)(rows - pos) * xistride : 0) : nullptr;
-    const unsigned long long sd = (seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed) ^ KNOWN_NOISE_DOMAIN;
+    const unsigned long long sd = run_key(seed, seed_dev) ^ KNOWN_NOISE_DOMAIN;
     const uint32_t sub = fresh ? (uint32_t)j : 0u;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
         const float m = mask[e % mask_numel];
@@ -1107,9 +1107,7 @@ __global__ void mask_blend_kernel(float* x, float* x2, long long numel, const fl
             }
             v = (m == 1.f) ? kn : m * kn + (1.f - m) * v;
         }
-        x[e] = v;
-        if (x2) { x2[e] = v; x2[numel + e] = v; }
-        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+        store_state(v, e, numel, x, x2, slot, snaps);
     }
 }
 
@@ -1561,8 +1559,8 @@ CDM_API int cdm_mse(const float* pred, const float* noise, long long n, double g
 }
 CDM_API int cdm_sample_prologue(int* ctr, int T, int* cur_i, float* t_cur, const float* sc_table, int sc_row, float* sc_cur,
                                 void* stream) {
-    hipLaunchKernelGGL(sample_prologue_kernel, dim3(1), dim3(256), 0, S(stream), ctr, T, cur_i, t_cur, sc_table, sc_row,
-                       sc_cur);
+    hipLaunchKernelGGL(sample_prologue_kernel, dim3(1), dim3(256), 0, S(stream), ctr, T, T, (const int*)nullptr, cur_i,
+                       (int*)nullptr, t_cur, sc_table, sc_row, sc_cur);      // the ancestral form: position = timestep
     return cdm_status();
 }
 CDM_API int cdm_denoise(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
@@ -1577,7 +1575,7 @@ CDM_API int cdm_sample_prologue_sub(int* ctr, int npos, int T, const int* steps,
                                     const float* sc_table, int sc_row, float* sc_cur, void* stream) {
     if (!ctr || !steps || !cur_i || !cur_k || !t_cur || npos < 1 || T < npos || (sc_table && (!sc_cur || sc_row < 0)))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_prologue_sub_kernel, dim3(1), dim3(256), 0, S(stream), ctr, npos, T, steps, cur_i, cur_k, t_cur,
+    hipLaunchKernelGGL(sample_prologue_kernel, dim3(1), dim3(256), 0, S(stream), ctr, npos, T, steps, cur_i, cur_k, t_cur,
                        sc_table, sc_row, sc_cur);
     return cdm_status();
 }

@@ -55,6 +55,31 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _draw_shortcut_row(nf: int, sets: int = 1):
+    """The random 1x1 shortcut conv(s) of one eval forward (diffusion_utilities.py:54), drawn from the CPU RNG as the
+    reference constructs them -> [weights of every set, then biases]; ``sets`` = 2 with CFG: cond before uncond."""
+    ws, bs = [], []
+    for _ in range(sets):
+        conv = nn.Conv2d(1, nf, kernel_size=1, stride=1, padding=0)
+        ws.append(conv.weight.detach().reshape(nf)); bs.append(conv.bias.detach())
+    return torch.cat(ws + bs)
+
+
+def _capture_steps(warm_up, step, K: int):
+    """The hipGraph of K calls of ``step(stream)``, captured on a side stream after one ``warm_up(stream)`` launch there
+    (every kernel's code object resident before the capture)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        warm_up(s.cuda_stream)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(K):
+            step(torch.cuda.current_stream().cuda_stream)
+    return g
+
+
 def sqrt_scalar_f32(v: torch.Tensor) -> torch.Tensor:
     """fp32 sqrt of every element as a 0-d tensor op computes it: IEEE correctly rounded, the same on every host
     (round(sqrt_fp64(x)) equals the correctly rounded fp32 sqrt: 53 >= 2 * 24 + 2 bits)."""
@@ -358,6 +383,10 @@ def check_inpaint(known, mask, n: int, H: int, known_noise: str = "fixed", in_ch
 class GraphSampler:
     """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed.
 
+    Every sampler runs the one ``_step`` defined here: ``_prologue`` (device counter -> timestep, shortcut row), the eval
+    forward, ``_update`` (the solver's kernel; here the reference's ancestral ``cdm_denoise``) and ``_blend``; and the one
+    ``prepare_rng``, whose z draws follow the solver's ``_draws_host_z``.  A solver subclass overrides those two.
+
     Masked (inpainting) sampling, ``inpaint="fixed" | "fresh"`` with ``mask_n`` = n or 1 (the mask's batch extent):
     ``cdm_mask_blend`` follows the step kernel of every step, in the captured graph and in the eager tail, and
     re-imposes ``known`` where ``mask`` is 1 at the noise level of the state just written (:func:`known_tables`; the
@@ -372,7 +401,7 @@ class GraphSampler:
                  save_rate: int = 20, z_source: str = "device", steps_per_graph: int = 10, seed: int = 1234,
                  snapshots: bool = True, use_graph: bool = True, positions: Optional[int] = None,
                  inpaint: Optional[str] = None, mask_n: Optional[int] = None):
-        """``positions``: the number of steps of a run when it is not T (DDIMSampler); it sizes the per-step tables."""
+        """``positions``: the number of steps of a run when it is not T (_StridedSampler); it sizes the per-step tables."""
         from .model import ContextUnet  # noqa: F401
         if inpaint is not None and inpaint not in KNOWN_NOISE_MODES:
             raise ValueError(f"inpaint must be None or one of {KNOWN_NOISE_MODES}, got {inpaint!r}")
@@ -422,35 +451,22 @@ class GraphSampler:
         self.K = max(1, int(steps_per_graph))
         self.use_graph = use_graph
         self.graph = None
-        self.cur_k = self.steps_t = None                     # the strided samplers set them after this constructor
-        self.inpaint = inpaint
+        self.cur_k = self.steps_t = None                     # the ancestral form: position = timestep (cdm_mask_blend)
+        self.inpaint, self.xi_table = inpaint, None
         if inpaint is not None:
             self.mask_n = mask_n
             self.known = torch.zeros(n * H * H, device=dev)
             self.mask = torch.zeros(mask_n * H * H, device=dev)
             self.ksab, self.ksomab = (torch.from_numpy(v).to(dev) for v in ktab)
-            xi_rows = 1 if inpaint == "fixed" else max(self.npos - 1, 1)
-            self.xi_table = E(xi_rows, n * H * H) if z_source == "host" else None
+            if z_source == "host":
+                self.xi_table = E(1 if inpaint == "fixed" else max(self.npos - 1, 1), n * H * H)
+
+    def _draws_host_z(self, p: int) -> bool:
+        """Whether position p of npos..1 takes a z from the CPU RNG in a host_z run (the solver's own rule)."""
+        return p > 1
 
     def _needs_z_table(self):
-        return self.z_source == "host"
-
-    def _draw_xi(self, host_z: bool, rows=None):
-        """Host xi of masked sampling: with ``rows`` None the "fixed" draw (before the loop over the steps), else the
-        "fresh" draw of one step, appended to ``rows``.  Nothing is drawn without inpainting or in device mode."""
-        if not host_z or self.inpaint is None:
-            return
-        if self.xi_table is None:
-            raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
-        if rows is None:
-            if self.inpaint == "fixed":
-                self.xi_table.copy_(torch.randn(self.n, 1, self.H, self.H).reshape(1, -1))
-        elif self.inpaint == "fresh":
-            rows.append(torch.randn(self.n, 1, self.H, self.H))
-
-    def _store_xi(self, rows):
-        if rows:
-            self.xi_table.copy_(torch.stack(rows).reshape(len(rows), -1))
+        return self.z_source == "host" and any(self._draws_host_z(p) for p in range(1, self.npos + 1))
 
     def _blend(self, s):
         """cdm_mask_blend on the state the step kernel has just written (no-op without inpainting)."""
@@ -463,61 +479,49 @@ class GraphSampler:
                              1 if self.inpaint == "fresh" else 0, self.seed, _p(self.zseed), _p(self.slot),
                              _p(self.snaps), s)
 
-    # RNG draws in the reference order ------------------------------------------------------------
-    def _draw_shortcut_row(self):
-        nf = self.model.n_feat
-        ws, bs = [], []
-        for _ in range(self.sets):
-            conv = nn.Conv2d(1, nf, kernel_size=1, stride=1, padding=0)
-            ws.append(conv.weight.detach().reshape(nf)); bs.append(conv.bias.detach())
-        return torch.cat(ws + bs)
-
     def prepare_rng(self, host_z: bool):
-        """Draw the per-step CPU-RNG quantities (and z in host mode) in reference order."""
-        n, H = self.n, self.H
-        rows, xis = [], []
-        zs = [] if host_z else None
-        self._draw_xi(host_z)
-        for i in range(self.T, 0, -1):
-            if host_z and i > 1:
-                zs.append(torch.randn(n, 1, H, H))
-            if i > 1:
-                self._draw_xi(host_z, xis)
-            rows.append(self._draw_shortcut_row())
+        """Draw the per-step CPU-RNG quantities in reference order, and with ``host_z`` z and the known-region xi too: the
+        "fixed" xi, then for each position p = npos..1 z (where the solver draws one), the "fresh" xi (p > 1), the
+        shortcut row(s).  ValueError, nothing drawn: ``host_z`` on a sampler built without the host tables."""
+        if host_z and self.z_source != "host":
+            raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
+        draw = lambda: torch.randn(self.n, 1, self.H, self.H)
+        if host_z and self.inpaint == "fixed":
+            self.xi_table.copy_(draw().reshape(1, -1))
+        rows, zs, xis = [], [], []
+        for p in range(self.npos, 0, -1):
+            if host_z and self._draws_host_z(p):
+                zs.append(draw())
+            if host_z and self.inpaint == "fresh" and p > 1:
+                xis.append(draw())
+            rows.append(_draw_shortcut_row(self.model.n_feat, self.sets))
         self.sc_table.copy_(torch.stack(rows))
-        if host_z and zs:
-            self.z_table.copy_(torch.stack(zs).reshape(self.T - 1, n * H * H))
-        self._store_xi(xis)
+        for table, drawn in ((self.z_table, zs), (self.xi_table, xis)):
+            if drawn:
+                table.copy_(torch.stack(drawn).reshape(len(drawn), -1))
 
-    # one step --------------------------------------------------------------------------------------
+    # one step: prologue -> eval forward -> update (the part a solver defines) -> blend ------------------------------
+    def _prologue(self, s):
+        lib().cdm_sample_prologue(_p(self.ctr), self.T, _p(self.cur_i), _p(self.t_cur), _p(self.sc_table), self.row,
+                                  _p(self.sc_cur), s)
+
+    def _update(self, s, eps, numel):
+        lib().cdm_denoise(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                          1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.sched.coef), _p(self.sched.sa),
+                          _p(self.sched.sb), _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
+                          _p(self.snaps), self.T, s)
+
     def _step(self, s):
-        lb = lib()
-        nf, n = self.model.n_feat, self.n
-        lb.cdm_sample_prologue(_p(self.ctr), self.T, _p(self.cur_i), _p(self.t_cur), _p(self.sc_table), self.row,
-                               _p(self.sc_cur), s)
-        half = self.sets * nf
-        sc_w, sc_b = self.sc_cur[:half], self.sc_cur[half:]
-        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, sc_w, sc_b, n, s)
-        numel = n * self.H * self.H
-        lb.cdm_denoise(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
-                       1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.sched.coef), _p(self.sched.sa),
-                       _p(self.sched.sb), _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
-                       _p(self.snaps), self.T, s)
+        self._prologue(s)
+        half = self.sets * self.model.n_feat
+        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, self.sc_cur[:half], self.sc_cur[half:],
+                               self.n, s)
+        self._update(s, eps, self.n * self.H * self.H)
         self._blend(s)
 
-    def _capture(self):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            # warm-up launch of every kernel before capture (code objects resident)
-            self.ctr.fill_(self.npos)
-            self._step(s.cuda_stream)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            for _ in range(self.K):
-                self._step(torch.cuda.current_stream().cuda_stream)
-        self.graph = g
+    def _warm_up(self, s):
+        self.ctr.fill_(self.npos)
+        self._step(s)
 
     def prepare(self):
         """Refresh the eval weight pack and capture the step graph (idempotent)."""
@@ -526,7 +530,7 @@ class GraphSampler:
             self.P, self.graph = P, None                    # parameters were re-homed: re-capture
         eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
         if self.use_graph and self.graph is None and self.npos >= self.K:
-            self._capture()
+            self.graph = _capture_steps(self._warm_up, self._step, self.K)
 
     def run(self, x_T: torch.Tensor, steps: Optional[int] = None, known=None, mask=None):
         """Run every step (T of them; S for the strided sampler), or the first ``steps``, from x_T [n,1,H,H].
@@ -567,13 +571,31 @@ class GraphSampler:
         return x, inter
 
 
-class DDIMSampler(GraphSampler):
+class _StridedSampler(GraphSampler):
+    """GraphSampler over the subsequence ``taus`` (:func:`timestep_subsequence`) of the T timesteps: the device counter
+    holds the position p = S..1 and ``cdm_sample_prologue_sub`` turns it into the timestep tau_p the network sees.  A
+    solver subclass validates its tables before this constructor allocates anything, and defines ``_update`` and
+    ``_draws_host_z``.  Snapshots follow the reference's rule on positions: ``snapshot_slots(S, save_rate)``."""
+
+    def __init__(self, model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
+                 use_graph, inpaint, mask_n):
+        self.taus, self.S = taus, len(taus)
+        super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
+        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=self.dev)
+        self.cur_k = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    def _prologue(self, s):
+        lib().cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
+                                      _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+
+
+class DDIMSampler(_StridedSampler):
     """Strided reverse diffusion: S of the T timesteps (:func:`timestep_subsequence`) with the update of
     :func:`ddim_tables`, on GraphSampler's buffers, RNG modes, snapshots and captured step graph.
 
-    The device counter holds the position p = S..1; ``cdm_sample_prologue_sub`` turns it into the timestep
-    tau_p the network sees, and ``cdm_ddim_step`` applies x <- (cx[p] x + ce[p] eps) + sigma[p] z.  Snapshots follow
-    the reference's rule on positions: ``snapshot_slots(S, save_rate)``.  CPU-RNG order (z_source="host"), for
+    At the position p = S..1 (:class:`_StridedSampler`) ``cdm_ddim_step`` applies
+    x <- (cx[p] x + ce[p] eps) + sigma[p] z.  CPU-RNG order (z_source="host"), for
     p = S..1: z (only when eta > 0 and p > 1), then the shortcut row(s), cond before uncond; eta = 0 draws no z at all.
     In "device" mode z is Philox stream tau_p of the per-run key, as the full sampler's stream i.
 
@@ -585,62 +607,32 @@ class DDIMSampler(GraphSampler):
                  steps=50, eta: float = 0.0, spacing="uniform", save_rate: int = 20, z_source: str = "device",
                  steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
                  inpaint: Optional[str] = None, mask_n: Optional[int] = None):
-        self.taus = timestep_subsequence(sched.T, steps, spacing)
-        self.S = len(self.taus)
+        taus = timestep_subsequence(sched.T, steps, spacing)
         self.eta = float(eta)
-        cx, ce, sg = ddim_tables(sched.ab_t, self.taus, self.eta)          # validates eta before anything is allocated
-        super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
-        dev = self.dev
-        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
-        self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(dev) for v in (cx, ce, sg))
-        self.cur_k = torch.zeros(1, dtype=torch.int32, device=dev)
+        tables = ddim_tables(sched.ab_t, taus, self.eta)                   # validates eta before anything is allocated
+        super().__init__(model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, inpaint, mask_n)
+        self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(self.dev) for v in tables)
 
-    def _needs_z_table(self):
-        return self.z_source == "host" and self.eta > 0 and self.S > 1
+    def _draws_host_z(self, p):
+        return self.eta > 0 and p > 1
 
-    def prepare_rng(self, host_z: bool):
-        n, H = self.n, self.H
-        rows, zs, xis = [], [], []
-        self._draw_xi(host_z)
-        for p in range(self.S, 0, -1):
-            if host_z and self.eta > 0 and p > 1:
-                zs.append(torch.randn(n, 1, H, H))
-            if p > 1:
-                self._draw_xi(host_z, xis)
-            rows.append(self._draw_shortcut_row())
-        self.sc_table.copy_(torch.stack(rows))
-        if zs:
-            if self.z_table is None:
-                raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
-            self.z_table.copy_(torch.stack(zs).reshape(self.S - 1, n * H * H))
-        self._store_xi(xis)
-
-    def _step(self, s):
-        lb = lib()
-        nf, n = self.model.n_feat, self.n
-        lb.cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
-                                   _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
-        half = self.sets * nf
-        sc_w, sc_b = self.sc_cur[:half], self.sc_cur[half:]
-        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, sc_w, sc_b, n, s)
-        numel = n * self.H * self.H
-        lb.cdm_ddim_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
-                         1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.cur_k), _p(self.cx), _p(self.ce),
-                         _p(self.sigma), self.S, _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
-                         _p(self.snaps), s)
-        self._blend(s)
+    def _update(self, s, eps, numel):
+        lib().cdm_ddim_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                            1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.cur_k), _p(self.cx), _p(self.ce),
+                            _p(self.sigma), self.S, _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
+                            _p(self.snaps), s)
 
 
-class DPMSolverSampler(GraphSampler):
+class DPMSolverSampler(_StridedSampler):
     """Strided reverse diffusion with the multistep update of :func:`dpmpp_tables` (DPM-Solver++ 2M; ``order=1`` is DDIM
     at eta = 0 written on the data prediction), on GraphSampler's buffers, snapshots and captured step graph.
 
-    As in DDIMSampler the device counter holds the position p = S..1 and ``cdm_sample_prologue_sub`` turns it into the
-    timestep; ``cdm_dpmpp_step`` applies the update and keeps the previous data prediction in ``dprev``, allocated here
+    At the position p = S..1 (:class:`_StridedSampler`) ``cdm_dpmpp_step`` applies the update and keeps the previous
+    data prediction in ``dprev``, allocated here
     once so a captured graph stays valid across runs (its stale contents are never read: c1 = 0 at the first position).
     The solver is deterministic: no z in any ``z_source``.  CPU-RNG order, for p = S..1: the shortcut row(s), cond
-    before uncond, and nothing else.  Snapshots: ``snapshot_slots(S, save_rate)`` on positions.
+    before uncond, and nothing else.
 
     Masked sampling (``inpaint``, ``mask_n``: see :class:`GraphSampler`) blends after every position, at the noise level
     of tau_{p-1}; ``dprev`` keeps the data prediction computed before the blend (from the state the network saw), the
@@ -653,44 +645,21 @@ class DPMSolverSampler(GraphSampler):
                  steps=20, order: int = 2, spacing="uniform", save_rate: int = 20, z_source: str = "device",
                  steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
                  inpaint: Optional[str] = None, mask_n: Optional[int] = None):
-        self.taus = timestep_subsequence(sched.T, steps, spacing)
-        self.S = len(self.taus)
-        tables = dpmpp_tables(sched.ab_t, self.taus, order)               # validates order before anything is allocated
+        taus = timestep_subsequence(sched.T, steps, spacing)
+        tables = dpmpp_tables(sched.ab_t, taus, order)                    # validates order before anything is allocated
         self.order = int(order)
-        super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
-        dev = self.dev
-        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=dev)
-        self.tables = tuple(torch.from_numpy(v).to(dev) for v in tables)  # sq, ra, c0, c1, cx, cd
-        self.cur_k = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.dprev = torch.empty(n * self.H * self.H, device=dev)
+        super().__init__(model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, inpaint, mask_n)
+        self.tables = tuple(torch.from_numpy(v).to(self.dev) for v in tables)  # sq, ra, c0, c1, cx, cd
+        self.dprev = torch.empty(n * self.H * self.H, device=self.dev)
 
-    def _needs_z_table(self):
+    def _draws_host_z(self, p):
         return False
 
-    def prepare_rng(self, host_z: bool):
-        rows, xis = [], []
-        self._draw_xi(host_z)
-        for p in range(self.S, 0, -1):
-            if p > 1:
-                self._draw_xi(host_z, xis)
-            rows.append(self._draw_shortcut_row())
-        self.sc_table.copy_(torch.stack(rows))
-        self._store_xi(xis)
-
-    def _step(self, s):
-        lb = lib()
-        nf, n = self.model.n_feat, self.n
-        lb.cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
-                                   _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
-        half = self.sets * nf
-        sc_w, sc_b = self.sc_cur[:half], self.sc_cur[half:]
-        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, sc_w, sc_b, n, s)
-        numel = n * self.H * self.H
-        lb.cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
-                          1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.S,
-                          _p(self.dprev), _p(self.slot), _p(self.snaps), s)
-        self._blend(s)
+    def _update(self, s, eps, numel):
+        lib().cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                             1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.S,
+                             _p(self.dprev), _p(self.slot), _p(self.snaps), s)
 
 
 class DDPM:
@@ -714,73 +683,61 @@ class DDPM:
     def denoise_add_noise(self, x, t, pred_noise, z=None):
         return denoise_add_noise(x, t, pred_noise, z, self.sched)
 
-    def _sampler(self, n, guide_w, params, save_rate, ddim=None, dpm=None, inpaint=None):
-        """The cached sampler of a configuration; ``ddim = (steps, eta, spacing)`` selects the strided one,
-        ``dpm = (steps, order, spacing)`` the multistep one (its key starts with a tag no DDIM key holds);
-        ``inpaint = (known_noise, mask batch extent)`` the masked form of any of them (a trailing tagged entry of the
-        key: the contents of known / mask are not part of it, one sampler and one captured graph serve them all)."""
+    def _sampler(self, n, guide_w, params, save_rate, solver=None, inpaint=None):
+        """The cached sampler of a configuration.  ``solver``: None, the ancestral GraphSampler, or (sampler class, steps,
+        eta or order, spacing) of a strided one; ``inpaint = (known_noise, mask batch extent)`` the masked form of any of
+        them (a trailing tagged entry of the key: the contents of known / mask are not part of it, one sampler and one
+        captured graph serve them all)."""
         key = (n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, self.z_source)
-        if ddim is not None:
-            steps, eta, spacing = ddim
-            key += (steps, float(eta), spacing if isinstance(spacing, str) else tuple(spacing))
-        elif dpm is not None:
-            steps, order, spacing = dpm
-            key += ("dpmpp", steps, order, spacing if isinstance(spacing, str) else tuple(spacing))
+        cls, sargs = GraphSampler, ()
+        if solver is not None:
+            cls, steps, opt, spacing = solver
+            sargs = (steps, opt, spacing)
+            key += (cls, steps, opt, spacing if isinstance(spacing, str) else tuple(spacing))
         ip = {}
         if inpaint is not None:
             key += (("inpaint",) + tuple(inpaint),)
             ip = dict(inpaint=inpaint[0], mask_n=inpaint[1])
         smp = self._samplers.get(key)
-        if smp is None and ddim is not None:
-            smp = self._samplers[key] = DDIMSampler(self.model, self.sched, n, guide_w, params, steps, eta, spacing,
-                                                    save_rate, self.z_source, seed=self.seed, **ip)
-        elif smp is None and dpm is not None:
-            smp = self._samplers[key] = DPMSolverSampler(self.model, self.sched, n, guide_w, params, steps, order,
-                                                         spacing, save_rate, self.z_source, seed=self.seed, **ip)
-        elif smp is None:
-            smp = self._samplers[key] = GraphSampler(self.model, self.sched, n, guide_w, params, save_rate,
-                                                     self.z_source, seed=self.seed, **ip)
+        if smp is None:
+            smp = self._samplers[key] = cls(self.model, self.sched, n, guide_w, params, *sargs, save_rate, self.z_source,
+                                            seed=self.seed, **ip)
         elif params is not None:
             smp.cbuf[:n] = params.to(smp.dev, torch.float32).reshape(n, -1)
         return smp
 
-    def _inpaint_args(self, known, mask, known_noise, n):
-        """Validated masked-sampling inputs -> (the ``inpaint`` entry of :meth:`_sampler`, run() keywords); (None, {})
-        without them.  Called before anything is drawn, so a ValueError leaves the CPU RNG where it was."""
-        known, mask = check_inpaint(known, mask, n, self.model.h, known_noise, self.model.in_channels)
-        if known is None:
-            return None, {}
-        return (known_noise, int(mask.shape[0])), dict(known=known, mask=mask)
-
     @torch.no_grad()
+    def _sample(self, solver, x_T, size, params, guide_w, save_rate, known, mask, known_noise):
+        """Every sample_* method.  ``x_T``: the noise images, or their number to draw them [n,1,size,size], and random
+        ``params`` when none are given, from the CPU RNG as the reference does.  The masked-sampling inputs are validated
+        before anything is drawn, so a ValueError leaves the CPU RNG where it was."""
+        draw = not torch.is_tensor(x_T)
+        assert not draw or size == self.model.h
+        n = x_T if draw else x_T.shape[0]
+        known, mask = check_inpaint(known, mask, n, self.model.h, known_noise, self.model.in_channels)
+        if draw:
+            x_T = torch.randn(n, 1, size, size)
+            if params is None:
+                params = torch.rand(n, self.n_cfeat)
+        smp = self._sampler(n, guide_w, params, save_rate, solver,
+                            None if known is None else (known_noise, int(mask.shape[0])))
+        smp.prepare_rng(host_z=self.z_source == "host")
+        return smp.run(x_T, known=known, mask=mask)
+
     def sample_ddpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, save_rate=20, *, known=None,
                     mask=None, known_noise="fixed"):
         """code/train_diffusion_condition.py:281-335 -> (samples, intermediate).  ``known`` [n,1,size,size] and ``mask``
         [n or 1,1,size,size] (keyword only, both or neither; 1 = known pixel, 0 = generated, between: a soft blend) run
         masked sampling with the known-region noise mode ``known_noise`` ("fixed" | "fresh", :class:`GraphSampler`);
         :func:`check_inpaint` lists what raises ValueError."""
-        assert size == self.model.h
-        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
-        host = self.z_source == "host"
-        x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as the reference
-        if params is None:
-            params = torch.rand(n_sample, self.n_cfeat)      # CPU RNG, as the reference
-        smp = self._sampler(n_sample, guide_w, params, save_rate, inpaint=ip)
-        smp.prepare_rng(host_z=host)
-        return smp.run(x_T, **kw)
+        return self._sample(None, n_sample, size, params, guide_w, save_rate, known, mask, known_noise)
 
-    @torch.no_grad()
     def sample_ddpm_from_noise(self, noise_images, params=None, save_rate=20, guide_w=0.0, *, known=None, mask=None,
                                known_noise="fixed"):
         """code/train_diffusion_condition.py:337-384 (and the unconditional code/train_diffusion.py:170-193).
         ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm` (noise_images is not blended)."""
-        n = noise_images.shape[0]
-        ip, kw = self._inpaint_args(known, mask, known_noise, n)
-        smp = self._sampler(n, guide_w, params, save_rate, inpaint=ip)
-        smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images, **kw)
+        return self._sample(None, noise_images, None, params, guide_w, save_rate, known, mask, known_noise)
 
-    @torch.no_grad()
     def sample_ddim(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=50, eta=0.0,
                     spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm on ``steps`` of the T timesteps (:class:`DDIMSampler`; ``spacing``: "uniform", "quadratic" or an
@@ -788,26 +745,15 @@ class DDPM:
         random params consume the CPU RNG as sample_ddpm does; eta = 0 is deterministic given x_T and the shortcut
         draws, eta = 1 has the ancestral sampler's variance.  Snapshots: snapshot_slots(steps, save_rate) on positions.
         ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm`."""
-        assert size == self.model.h
-        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
-        x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
-        if params is None:
-            params = torch.rand(n_sample, self.n_cfeat)
-        smp = self._sampler(n_sample, guide_w, params, save_rate, (steps, eta, spacing), inpaint=ip)
-        smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(x_T, **kw)
+        return self._sample((DDIMSampler, steps, float(eta), spacing), n_sample, size, params, guide_w, save_rate, known,
+                            mask, known_noise)
 
-    @torch.no_grad()
     def sample_ddim_from_noise(self, noise_images, params=None, steps=50, eta=0.0, spacing="uniform", save_rate=20,
                                guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_ddim`)."""
-        n = noise_images.shape[0]
-        ip, kw = self._inpaint_args(known, mask, known_noise, n)
-        smp = self._sampler(n, guide_w, params, save_rate, (steps, eta, spacing), inpaint=ip)
-        smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images, **kw)
+        return self._sample((DDIMSampler, steps, float(eta), spacing), noise_images, None, params, guide_w, save_rate,
+                            known, mask, known_noise)
 
-    @torch.no_grad()
     def sample_dpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=20, order=2,
                    spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm on ``steps`` of the T timesteps with the second-order multistep update (:class:`DPMSolverSampler`;
@@ -815,24 +761,14 @@ class DDPM:
         random params consume the CPU RNG as sample_ddpm does; the run is deterministic given x_T and the shortcut
         draws.  Snapshots: snapshot_slots(steps, save_rate) on positions.  ``known`` / ``mask`` / ``known_noise``:
         masked sampling, as in :meth:`sample_ddpm` (keep "fixed" here, see :class:`DPMSolverSampler`)."""
-        assert size == self.model.h
-        ip, kw = self._inpaint_args(known, mask, known_noise, n_sample)
-        x_T = torch.randn(n_sample, 1, size, size)          # CPU RNG, as sample_ddpm
-        if params is None:
-            params = torch.rand(n_sample, self.n_cfeat)
-        smp = self._sampler(n_sample, guide_w, params, save_rate, dpm=(steps, order, spacing), inpaint=ip)
-        smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(x_T, **kw)
+        return self._sample((DPMSolverSampler, steps, order, spacing), n_sample, size, params, guide_w, save_rate, known,
+                            mask, known_noise)
 
-    @torch.no_grad()
     def sample_dpm_from_noise(self, noise_images, params=None, steps=20, order=2, spacing="uniform", save_rate=20,
                               guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_dpm`)."""
-        n = noise_images.shape[0]
-        ip, kw = self._inpaint_args(known, mask, known_noise, n)
-        smp = self._sampler(n, guide_w, params, save_rate, dpm=(steps, order, spacing), inpaint=ip)
-        smp.prepare_rng(host_z=self.z_source == "host")
-        return smp.run(noise_images, **kw)
+        return self._sample((DPMSolverSampler, steps, order, spacing), noise_images, None, params, guide_w, save_rate,
+                            known, mask, known_noise)
 
     def inpaint(self, known, mask, params=None, guide_w=0.0, sampler="ddpm", **sampler_kwargs):
         """Complete the maps ``known`` [n,1,H,H] where ``mask`` [n or 1,1,H,H] is 0 -> (samples, intermediate).
@@ -874,12 +810,4 @@ def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.
         if solver != "ddim":
             raise ValueError(f"solver must be 'ddim' or 'dpmpp', got {solver!r}")
         return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing, **ipk)[0]
-    if params is None:
-        ip, kw = d._inpaint_args(known, mask, known_noise, n_sample)
-        x_T = torch.randn(n_sample, 1, size, size)
-        params = torch.rand(n_sample, 6 if model.n_cfeat == 6 else model.n_cfeat)
-        smp = d._sampler(n_sample, guide_w, params, 20, inpaint=ip)
-        smp.prepare_rng(host_z=z_source == "host")
-        return smp.run(x_T, **kw)[0]
-    x, _ = d.sample_ddpm(n_sample, size, device, params, guide_w, **ipk)
-    return x
+    return d.sample_ddpm(n_sample, size, device, params, guide_w, **ipk)[0]

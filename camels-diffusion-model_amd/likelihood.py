@@ -26,18 +26,9 @@ import math
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
 from ._lib import lib
-from .diffusion import Schedule
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from .diffusion import Schedule, _capture_steps, _draw_shortcut_row, _p, _s
 
 
 def _split_batch(item):
@@ -98,19 +89,13 @@ class _EvalRun:
 
     def capture(self, K: int):
         ev = self.ev
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
         rng = ev.rng_ctr.clone()
-        with torch.cuda.stream(s):
+
+        def warm_up(s):
             self.ctr.fill_(ev.T)
-            self.step(s.cuda_stream, None, None, ev.sched.omab)     # warm-up: every kernel resident
+            self.step(s, None, None, ev.sched.omab)                 # every kernel resident
             ev.rng_ctr.copy_(rng)                                   # ... without consuming a noise stream
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            for _ in range(K):
-                self.step(torch.cuda.current_stream().cuda_stream, ev.nll_mul, ev.nll_div, ev.sched.omab)
-        self.graph = g
+        self.graph = _capture_steps(warm_up, lambda s: self.step(s, ev.nll_mul, ev.nll_div, ev.sched.omab), K)
 
     def load(self, x, c):
         B, dev = self.B, self.ev.dev
@@ -165,11 +150,6 @@ class LikelihoodEvaluator:
                 r.graph = None
         eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
 
-    def _shortcut_row(self):
-        nf = self.model.n_feat
-        conv = nn.Conv2d(1, nf, kernel_size=1, stride=1, padding=0)       # diffusion_utilities.py:54
-        return torch.cat([conv.weight.detach().reshape(nf), conv.bias.detach()])
-
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def batch_nll(self, x, c=None) -> torch.Tensor:
@@ -185,7 +165,7 @@ class LikelihoodEvaluator:
         for t in range(1, T + 1):                       # reference order: noise_t, then the model's shortcut
             if host:
                 zs[T - t] = torch.randn(x.shape).reshape(-1)
-            rows[T - t] = self._shortcut_row()
+            rows[T - t] = _draw_shortcut_row(self.model.n_feat)
         r.sc_table.copy_(rows)
         if host:
             r.noise.copy_(zs)
@@ -217,7 +197,7 @@ class LikelihoodEvaluator:
             ti = int(t)
             if host:
                 r.noise[0].copy_(torch.randn(x.shape).reshape(-1))
-            r.sc_cur.copy_(self._shortcut_row())
+            r.sc_cur.copy_(_draw_shortcut_row(self.model.n_feat))
             r.cur_i.fill_(ti)
             r.t_cur.fill_(float(t / T))                # torch.tensor([t / timesteps]) with a tensor t (fp32 divide)
             r._body(s, self.elbo_mul if ti > 1 else None, self.elbo_div, self.sqrt_omab, 0)   # noise row 0

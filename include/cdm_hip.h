@@ -390,8 +390,13 @@ int cdm_mse_accum(const float* pred, const float* noise, long long nstride, int 
  * nonfinite (optional): += 1 when the loss is NaN / inf (SURVEY §5 failure guard; read once per epoch) */
 int cdm_mse(const float* pred, const float* noise, long long n, double grad_numel, float* dpred, float* partial, int nb,
             float* loss_out, float* dbias_out, int* nonfinite, void* stream);
-/* sampler: per-step prologue (device step counter) and denoise_add_noise + CFG combine
- * (code/train_diffusion_condition.py:274-279, 312-333) */
+/* sampler.  One step of every sampler is: a prologue (below or cdm_sample_prologue_sub), the eval forward, one update
+ * (cdm_denoise, cdm_ddim_step or cdm_dpmpp_step) and, in masked sampling, cdm_mask_blend.  The two prologues launch one
+ * kernel; the update and blend kernels share the CFG combine eps = eu + w (ec - eu), the per-run key seed ^ *seed_dev
+ * and the write-out (x, both halves of x2, the snapshot slot).
+ * Ancestral prologue (device step counter; code/train_diffusion_condition.py:312-333): i = *ctr; *ctr = i - 1;
+ * cur_i = i; t_cur = (float)((double)i / T); shortcut row T - i of sc_table.  A counter outside 1..T writes and reads
+ * nothing.  cdm_denoise: denoise_add_noise + CFG combine (:274-279). */
 int cdm_sample_prologue(int* ctr, int T, int* cur_i, float* t_cur, const float* sc_table, int sc_row, float* sc_cur,
                         void* stream);
 /* z: z_table[(T - i) * zstride + e] when given, else Philox keyed by seed ^ *seed_dev (seed_dev optional: a
@@ -403,7 +408,7 @@ int cdm_denoise(const float* xin, float* x, float* x2, long long numel, const fl
 /* strided (DDIM) sampler over the timestep subsequence steps[0..npos] (steps[0] = 0 < steps[1] < ... < steps[npos] = T;
  * the device counter holds the position k = npos..1).  Prologue: cur_k = k, cur_i = i = steps[k],
  * t_cur = (float)((double)i / T), *ctr = k - 1, shortcut row npos - k of sc_table.  A counter outside 1..npos writes
- * nothing (and the step kernel then does nothing either). */
+ * nothing (and the step kernel then does nothing either).  cdm_sample_prologue is this with npos = T and steps[k] = k. */
 int cdm_sample_prologue_sub(int* ctr, int npos, int T, const int* steps, int* cur_i, int* cur_k, float* t_cur,
                             const float* sc_table, int sc_row, float* sc_cur, void* stream);
 /* x <- (cx[k] x + ce[k] eps) + sigma[k] z with separate fp32 roundings; eps = eu + w (ec - eu) when cfg.  cx / ce /
