@@ -5,8 +5,9 @@ Drop-in for the reference's ContextUnet module API (ContextUnet.py), its diffusi
 repo-root ``cdm_amd.py`` shim maps the hyphenated directory to that name).
 """
 from ._lib import lib  # noqa: F401
-from .diffusion import (DDPM, DDIMSampler, DPMSolverSampler, GraphSampler, Schedule, check_inpaint,  # noqa: F401
-                        ddim_tables, denoise_add_noise, dpmpp_tables, known_tables, perturb_input, sample_ddpm,
+from .diffusion import (DDPM, DDIMSampler, DPMSolverSampler, GraphSampler, Program, Schedule,  # noqa: F401
+                        check_inpaint, ddim_tables, ddim_tables_from_pairs, denoise_add_noise, dpmpp_tables,
+                        dpmpp_tables_from_pairs, known_tables, perturb_input, resample_program, sample_ddpm,
                         timestep_subsequence)
 from .likelihood import (LikelihoodEvaluator, calculate_elbo_and_bpd, calculate_elbo_and_bpd_batch,  # noqa: F401
                          calculate_elbo_and_bpd_dataset, calculate_likelihood)
@@ -17,7 +18,8 @@ from .trainer import Trainer  # noqa: F401
 
 __all__ = ["ContextUnet", "EmbedFC", "ResidualConvBlock", "UnetDown", "UnetUp", "lib", "DDPM", "GraphSampler",
            "DDIMSampler", "ddim_tables", "timestep_subsequence", "DPMSolverSampler", "dpmpp_tables",
-           "known_tables", "check_inpaint",
+           "known_tables", "check_inpaint", "Program", "resample_program", "ddim_tables_from_pairs",
+           "dpmpp_tables_from_pairs",
            "Schedule", "denoise_add_noise", "perturb_input", "sample_ddpm", "Trainer", "LikelihoodEvaluator",
            "calculate_likelihood", "calculate_elbo_and_bpd", "calculate_elbo_and_bpd_batch",
            "calculate_elbo_and_bpd_dataset", "power_spectrum", "power_spectra", "compare_power_spectra",

@@ -1016,16 +1016,22 @@ __global__ void denoise_kernel(const float* xin, float* x, float* x2, long long 
 // cx / ce / sigma [S+1]: host tables (diffusion.ddim_tables).  z is neither read nor drawn when sigma[k] == 0 (eta = 0,
 // and the last position); else z_table[(S-k)][e] when given, else Philox(run_key, stream i) keyed by the timestep.
 // Write-out: store_state, slot[k].  A k outside 1..S writes nothing.
+// BY_POSITION (a position program, where one timestep is visited more than once: cdm_ddim_step_pos): the device z is
+// Philox keyed by run_key ^ STEP_NOISE_DOMAIN, stream k, so every visit draws its own; cur_i is not read.  The constant
+// is the ASCII of "pos_step" and has no other meaning.
+constexpr unsigned long long STEP_NOISE_DOMAIN = 0x706F735F73746570ull;
+template <bool BY_POSITION>
 __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
                                  float w, const int* cur_i, const int* cur_k, const float* cx, const float* ce,
                                  const float* sigma, int S, const float* z_table, long long zstride,
                                  unsigned long long seed, const long long* seed_dev, const int* snap_slot, float* snaps) {
 #pragma clang fp contract(off)  // separate fp32 roundings: (cx*x + ce*ep) + sg*z as a torch CPU restatement computes it
-    const int i = *cur_i, k = *cur_k;
+    const int k = *cur_k;
+    const int i = BY_POSITION ? k : *cur_i;
     if (k < 1 || k > S) return;
     const float a = cx[k], c = ce[k], sg = sigma[k];
     const int slot = snap_slot ? snap_slot[k] : -1;
-    const unsigned long long sd = run_key(seed, seed_dev);
+    const unsigned long long sd = BY_POSITION ? run_key(seed, seed_dev) ^ STEP_NOISE_DOMAIN : run_key(seed, seed_dev);
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
         float v = a * xin[e] + c * cfg_eps(eps, numel, e, cfg, w);
         if (sg != 0.f) {
@@ -1108,6 +1114,59 @@ __global__ void mask_blend_kernel(float* x, float* x2, long long numel, const fl
             v = (m == 1.f) ? kn : m * kn + (1.f - m) * v;
         }
         store_state(v, e, numel, x, x2, slot, snaps);
+    }
+}
+
+// The blend of a position program (resampling, late start) and its forward jump, in one pass over the state.
+// The position p = *cur_k of 1..npos landed on the timestep j = land_t[p] (a table of its own: the prologue's timestep
+// table is not consulted, and a program visits one timestep at several positions).
+//   v = mask_blend_kernel's blend at the level j, same roundings and the same m == 0 / m == 1 / j == 0 rules; a null
+//       mask is no blend, v = x (known, sab and somab are then not read)
+//   snapshot slot of p <- v                      (the blended state, before the jump)
+//   x <- fa[p]*v + fb[p]*zeta  where fb[p] != 0  (re-noised forward from j to the jump target, every pixel, the known
+//                                                 ones too; the two products and the sum each their own fp32 rounding)
+//   x <- v                     where fb[p] == 0  (no jump: zeta neither read nor drawn)
+// zeta: row npos - p of zeta_table when given, else Philox keyed by run_key ^ JUMP_NOISE_DOMAIN, stream p.  The "fresh"
+// xi is row npos - p of xi_table or Philox run_key ^ KNOWN_NOISE_DOMAIN, stream p (by position, not by j); "fixed" is
+// row 0 or stream 0, as in mask_blend_kernel.  The constant is the ASCII of "jumpzeta" and has no other meaning.
+// A position outside 1..npos, or a j outside 0..T, writes nothing.
+constexpr unsigned long long JUMP_NOISE_DOMAIN = 0x6A756D707A657461ull;
+__global__ void mask_blend_jump_kernel(float* x, float* x2, long long numel, const float* known, const float* mask,
+                                       long long mask_numel, const int* cur_k, const int* land_t, int npos, int T,
+                                       const float* sab, const float* somab, const float* fa, const float* fb,
+                                       const float* xi_table, long long xistride, int fresh, const float* zeta_table,
+                                       long long zetastride, unsigned long long seed, const long long* seed_dev,
+                                       const int* snap_slot, float* snaps) {
+#pragma clang fp contract(off)  // separate fp32 roundings, as a torch CPU restatement computes them
+    const int pos = *cur_k;
+    if (pos < 1 || pos > npos) return;
+    const int j = land_t[pos];
+    if (j < 0 || j > T) return;
+    const int slot = snap_slot ? snap_slot[pos] : -1;
+    const float sa = mask ? sab[j] : 1.f, so = mask ? somab[j] : 0.f;
+    const float ja = fa[pos], jb = fb[pos];
+    const float* xr = xi_table ? xi_table + (fresh ? (long long)(npos - pos) * xistride : 0) : nullptr;
+    const float* zr = zeta_table ? zeta_table + (long long)(npos - pos) * zetastride : nullptr;
+    const unsigned long long key = run_key(seed, seed_dev);
+    const unsigned long long sd = key ^ KNOWN_NOISE_DOMAIN, sdz = key ^ JUMP_NOISE_DOMAIN;
+    const uint32_t sub = fresh ? (uint32_t)pos : 0u;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
+        float v = x[e];
+        const float m = mask ? mask[e % mask_numel] : 0.f;
+        if (m != 0.f) {
+            float kn = known[e];
+            if (j >= 1) {
+                const float xi = xr ? xr[e] : philox_normal(sd, sub, e);
+                kn = sa * kn + so * xi;
+            }
+            v = (m == 1.f) ? kn : m * kn + (1.f - m) * v;
+        }
+        if (slot >= 0) snaps[(long long)slot * numel + e] = v;
+        if (jb != 0.f) {
+            const float zeta = zr ? zr[e] : philox_normal(sdz, (uint32_t)pos, e);
+            v = ja * v + jb * zeta;
+        }
+        store_state(v, e, numel, x, x2, -1, snaps);
     }
 }
 
@@ -1587,8 +1646,20 @@ CDM_API int cdm_ddim_step(const float* xin, float* x, float* x2, long long numel
         (snap_slot && !snaps))
         return (int)hipErrorInvalidValue;
     if (numel == 0) return 0;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg, w,
-                       cur_i, cur_k, cx, ce, sigma, npos, z_table, zstride, seed, seed_dev, snap_slot, snaps);
+    hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg,
+                       w, cur_i, cur_k, cx, ce, sigma, npos, z_table, zstride, seed, seed_dev, snap_slot, snaps);
+    return cdm_status();
+}
+CDM_API int cdm_ddim_step_pos(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                              const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
+                              const float* z_table, long long zstride, unsigned long long seed,
+                              const long long* seed_dev, const int* snap_slot, float* snaps, void* stream) {
+    if (!xin || !x || !eps || !cur_k || !cx || !ce || !sigma || npos < 1 || numel <= 0 || zstride < 0 ||
+        (snap_slot && !snaps))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(nblocks(numel)), dim3(256), 0, S(stream), xin, x, x2, numel, eps, cfg,
+                       w, (const int*)nullptr, cur_k, cx, ce, sigma, npos, z_table, zstride, seed, seed_dev, snap_slot,
+                       snaps);
     return cdm_status();
 }
 CDM_API int cdm_dpmpp_step(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
@@ -1616,6 +1687,21 @@ CDM_API int cdm_mask_blend(float* x, float* x2, long long numel, const float* kn
     hipLaunchKernelGGL(mask_blend_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), x, x2, numel, known, mask,
                        mask_numel, cur_i, cur_k, steps, npos, T, sab, somab, xi_table, xistride, fresh, seed, seed_dev,
                        snap_slot, snaps);
+    return cdm_status();
+}
+CDM_API int cdm_mask_blend_jump(float* x, float* x2, long long numel, const float* known, const float* mask,
+                                long long mask_numel, const int* cur_k, const int* land_t, int npos, int T,
+                                const float* sab, const float* somab, const float* fa, const float* fb,
+                                const float* xi_table, long long xistride, int fresh, const float* zeta_table,
+                                long long zetastride, unsigned long long seed, const long long* seed_dev,
+                                const int* snap_slot, float* snaps, void* stream) {
+    if (numel <= 0 || !x || !cur_k || !land_t || !fa || !fb || npos < 1 || T < 1 || xistride < 0 || zetastride < 0 ||
+        (snap_slot && !snaps))
+        return (int)hipErrorInvalidValue;
+    if (mask && (!known || !sab || !somab || mask_numel <= 0 || numel % mask_numel != 0)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_blend_jump_kernel, dim3(nblocks(numel)), dim3(256), 0, S(stream), x, x2, numel, known, mask,
+                       mask_numel, cur_k, land_t, npos, T, sab, somab, fa, fb, xi_table, xistride, fresh, zeta_table,
+                       zetastride, seed, seed_dev, snap_slot, snaps);
     return cdm_status();
 }
 static int adam_launch(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* state,

@@ -33,10 +33,15 @@ Masked (inpainting) sampling (not in the reference): every sampler above takes `
 re-imposes the known pixels, noised to the level of the state (:func:`known_tables`), after every step with one more
 kernel on the step graph (``cdm_mask_blend``; :class:`GraphSampler` has the definition); ``DDPM.inpaint`` is the
 convenience entry point.
+
+Position programs (not in the reference): the strided samplers take ``resample=`` / ``jump=`` (RePaint's resampling of a
+masked run) and ``t_start=`` (a late start, SDEdit; ``DDPM.refine`` is its entry point) and then walk the positions of
+:func:`resample_program` with per-position tables, a DDIM step keyed by the position and ``cdm_mask_blend_jump``
+(:class:`_StridedSampler` has the definition).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -349,6 +354,177 @@ def known_tables(ab_t):
     return sab.astype(np.float32), somab.astype(np.float32)
 
 
+class Program(NamedTuple):
+    """A position program (:func:`resample_program`): arrays of P + 1 entries indexed by the position p = P..1 in the
+    order it runs, entry 0 unused."""
+    from_t: np.ndarray      # int32: the timestep i the network sees
+    land_t: np.ndarray      # int32: the timestep j the update lands on
+    up_t: np.ndarray        # int32: the timestep u the state is re-noised to after the blend; == land_t: no jump
+    fa: np.ndarray          # fp32: sqrt(ab_u / ab_j); 1 exactly where there is no jump
+    fb: np.ndarray          # fp32: sqrt(1 - ab_u / ab_j); 0 exactly where there is no jump
+
+    @property
+    def P(self) -> int:
+        return self.from_t.size - 1
+
+
+def _ab64(ab_t):
+    if torch.is_tensor(ab_t):
+        ab_t = ab_t.detach().cpu().numpy()
+    return np.asarray(ab_t, dtype=np.float32).astype(np.float64).reshape(-1)
+
+
+def _posint(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    return int(v)
+
+
+def resample_program(ab_t, taus, jump: int = 1, resamples: int = 1, t_start: Optional[int] = None) -> Program:
+    """The walk over the timesteps ``taus`` (ascending, :func:`timestep_subsequence`; tau_0 = 0) of a run with RePaint's
+    resampling jumps (Lugmayr et al. 2022, get_schedule_jump) and / or a late start (SDEdit) -> :class:`Program`.
+
+    Late start: only the taus <= ``t_start`` are kept (S' of them; None keeps all) and the run starts at tau_S'.
+    Resampling, ``resamples`` = R and ``jump`` = J counted in positions: the state indices k that are multiples of J with
+    J <= k <= S' - J are jump points, each good for R - 1 jumps.  From k = S', while k > 0: emit a position from
+    i = tau_k landing on j = tau_{k-1}; k -= 1; if k is a jump point with jumps left, use one: the position just emitted
+    is marked with the target u = tau_{k+J} (after its blend the state is re-noised from j to u,
+    x_u = fa x_j + fb zeta with fa = sqrt(ab_u / ab_j), fb = sqrt(1 - ab_u / ab_j)) and k += J.  A used jump is never
+    restored.  P = S' + (R - 1) J (S' // J - 1) positions; the first emitted is p = P, the last p = 1.
+
+    ``ab_t`` is the fp32 table of the Schedule; the arithmetic is fp64 numpy, rounded once to fp32, as in
+    :func:`ddim_tables`.  Pure host function.  ValueError: ``taus`` not a valid subsequence of 1..T, ``jump`` or
+    ``resamples`` not an integer >= 1, ``t_start`` outside 1..T or below tau_1, R > 1 with no jump point (S' < 2 J)."""
+    ab = _ab64(ab_t)
+    T = ab.size - 1
+    tau = timestep_subsequence(T, None, taus)
+    J, R = _posint("jump", jump), _posint("resamples", resamples)
+    if t_start is not None:
+        if isinstance(t_start, bool) or int(t_start) != t_start or not 1 <= int(t_start) <= T:
+            raise ValueError(f"t_start must be an integer in 1..T = {T}, got {t_start!r}")
+        tau = [t for t in tau if t <= int(t_start)]
+        if not tau:
+            raise ValueError(f"t_start = {t_start} lies below the first timestep of the run")
+    S = len(tau)
+    if R > 1 and S < 2 * J:
+        raise ValueError(f"resamples = {R} needs a jump point: {S} positions are fewer than 2 * jump = {2 * J}")
+    tau = [0] + tau
+    left = {k: R - 1 for k in range(J, S - J + 1, J)}
+    frm, land, up = [0], [0], [0]
+    k = S
+    while k > 0:
+        frm.append(tau[k]); land.append(tau[k - 1]); up.append(tau[k - 1])
+        k -= 1
+        if left.get(k, 0) > 0:
+            left[k] -= 1
+            up[-1] = tau[k + J]
+            k += J
+    P = len(frm) - 1
+    assert P == S + (R - 1) * J * (S // J - 1 if S >= 2 * J else 0)
+    frm, land, up = (np.array(v[:1] + v[:0:-1], dtype=np.int64) for v in (frm, land, up))   # emitted first = position P
+    ab[0] = 1.0                                               # tau_0 = 0: ab_0 = 1 by definition
+    with np.errstate(divide="ignore", invalid="ignore"):     # reported below
+        ratio = ab[up] / ab[land]
+        fa, fb = np.sqrt(ratio), np.sqrt(1 - ratio)
+    stay = up == land
+    fa[stay], fb[stay] = 1.0, 0.0
+    if not (np.isfinite(fa).all() and np.isfinite(fb).all()):
+        raise ValueError("the schedule gives non-finite jump tables (ab_t must lie in (0, 1] and decrease)")
+    return Program(frm.astype(np.int32), land.astype(np.int32), up.astype(np.int32), fa.astype(np.float32),
+                   fb.astype(np.float32))
+
+
+def _pairs(ab_t, from_t, land_t):
+    """(i, j, ab_i, ab_j) of the positions 1..P of a program's (from_t, land_t) tables, validated."""
+    ab = _ab64(ab_t)
+    i, j = (np.asarray(v).astype(np.int64).reshape(-1)[1:] for v in (from_t, land_t))
+    if i.size < 1 or i.size != j.size:
+        raise ValueError("from_t and land_t must have the same P + 1 >= 2 entries")
+    if (j < 0).any() or (i <= j).any() or (i >= ab.size).any():
+        raise ValueError(f"every position must descend, 0 <= land_t < from_t <= T = {ab.size - 1}")
+    ab_i, ab_j = ab[i], ab[j]
+    ab_j[j == 0] = 1.0                                        # tau_0 = 0: ab_0 = 1 by definition
+    return i, j, ab_i, ab_j
+
+
+def ddim_tables_from_pairs(ab_t, from_t, land_t, eta: float = 0.0):
+    """:func:`ddim_tables` for the positions of a :class:`Program`: (cx, ce, sigma) of P + 1 entries, the step of
+    position p going from from_t[p] to land_t[p] (entry 0 of the two is ignored).  The same expressions on the same
+    numbers: for the plain program of ``taus`` (no jump, no late start) the result is ddim_tables' bit for bit."""
+    eta = float(eta)
+    if not (eta >= 0.0) or not np.isfinite(eta):
+        raise ValueError(f"eta must be finite and >= 0, got {eta}")
+    i, j, ab_i, ab_j = _pairs(ab_t, from_t, land_t)
+    with np.errstate(divide="ignore", invalid="ignore"):     # a degenerate schedule is reported below
+        sigma = eta * np.sqrt((1 - ab_j) / (1 - ab_i)) * np.sqrt(1 - ab_i / ab_j)
+        sigma[j == 0] = 0.0
+        rad = 1 - ab_j - sigma * sigma
+        if (rad < 0).any():
+            raise ValueError(f"eta = {eta} makes sigma^2 exceed 1 - ab_j at position {int(np.argmax(rad < 0)) + 1}")
+        cx = np.sqrt(ab_j / ab_i)
+        ce = np.sqrt(rad) - np.sqrt(ab_j * (1 - ab_i) / ab_i)
+    out = []
+    for v, v0 in ((cx, 1.0), (ce, 0.0), (sigma, 0.0)):
+        if not np.isfinite(v).all():
+            raise ValueError("the schedule gives non-finite DDIM coefficients (ab_t must lie in (0, 1) for t >= 1)")
+        out.append(np.concatenate([[v0], v]).astype(np.float32))
+    return tuple(out)
+
+
+def dpmpp_tables_from_pairs(ab_t, from_t, land_t, up_t=None, order: int = 2, dtype=np.float32):
+    """:func:`dpmpp_tables` for the positions of a :class:`Program`: (sq, ra, c0, c1, cx, cd) of P + 1 entries.
+
+    Position p is second order (c1 != 0) only if the position before it exists (p < P), that position had no jump after
+    it (up_t[p + 1] == land_t[p + 1]; ``up_t`` None: no jumps) and p does not land on 0; then r = h_{p+1} / h_p with that
+    previous position's own h.  After a jump the history is dropped, c1 = 0 as at the first position: the kept data
+    prediction belongs to a state that was re-noised since.  The same expressions on the same numbers as dpmpp_tables:
+    bit-equal to it for the plain program of ``taus``."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order!r}")
+    i, j, ab_i, ab_j = _pairs(ab_t, from_t, land_t)
+    P = i.size
+    land = np.asarray(land_t).astype(np.int64).reshape(-1)[1:]
+    up = land if up_t is None else np.asarray(up_t).astype(np.int64).reshape(-1)[1:]
+    if up.size != P:
+        raise ValueError("up_t must have the P + 1 entries of from_t")
+    bad = ValueError("the schedule gives non-finite DPM-Solver++ coefficients (ab_t must lie in (0, 1) for t >= 1 and "
+                     "decrease along the timesteps)")
+    with np.errstate(divide="ignore", invalid="ignore"):     # a degenerate schedule is reported below
+        al_i, al_j = np.sqrt(ab_i), np.sqrt(ab_j)
+        sg_i, sg_j = np.sqrt(1 - ab_i), np.sqrt(1 - ab_j)
+        sq, ra = sg_i, 1 / al_i
+        cx = sg_j / sg_i
+        cd = al_j - sg_j * al_i / sg_i
+        h = np.log(al_j / sg_j) - np.log(al_i / sg_i)        # +inf where the position lands on 0 (sigma_j = 0)
+        c0, c1 = np.ones(P), np.zeros(P)
+        if order == 2 and P > 1:
+            second = np.zeros(P, dtype=bool)
+            second[:-1] = (up[1:] == land[1:]) & (j[:-1] != 0)
+            q = np.nonzero(second)[0]
+            r = h[q + 1] / h[q]
+            c0[q], c1[q] = 1 + 1 / (2 * r), -1 / (2 * r)
+    if not (h > 0).all():
+        raise bad
+    out = []
+    for v, v0 in ((sq, 0.0), (ra, 1.0), (c0, 1.0), (c1, 0.0), (cx, 1.0), (cd, 0.0)):
+        if not np.isfinite(v).all():
+            raise bad
+        out.append(np.concatenate([[v0], v]).astype(dtype))
+    return tuple(out)
+
+
+def _program(ab_t, taus, resample, jump, t_start, inpaint):
+    """The program of a strided sampler's (resample, jump, t_start), or None when all three are at their defaults: the
+    plain walk, which keeps the kernels, buffers and RNG walk it had before programs existed.  ValueError: what
+    :func:`resample_program` raises, and resample > 1 on a sampler without a mask (there is nothing to harmonise)."""
+    if (resample, jump, t_start) == (1, 1, None) and not any(isinstance(v, bool) for v in (resample, jump)):
+        return None
+    prog = resample_program(ab_t, taus, jump, resample, t_start)
+    if resample > 1 and inpaint is None:
+        raise ValueError("resample > 1 re-noises towards a known region: it needs masked sampling (known= and mask=)")
+    return prog
+
+
 KNOWN_NOISE_MODES = ("fixed", "fresh")
 
 
@@ -468,6 +644,14 @@ class GraphSampler:
     def _needs_z_table(self):
         return self.z_source == "host" and any(self._draws_host_z(p) for p in range(1, self.npos + 1))
 
+    def _lands_above_zero(self, p: int) -> bool:
+        """Whether position p lands on a timestep >= 1 (the blend there needs a xi)."""
+        return p > 1
+
+    def _jumps(self, p: int) -> bool:
+        """Whether the state is re-noised forward after position p (a position program, _StridedSampler)."""
+        return False
+
     def _blend(self, s):
         """cdm_mask_blend on the state the step kernel has just written (no-op without inpainting)."""
         if self.inpaint is None:
@@ -481,8 +665,9 @@ class GraphSampler:
 
     def prepare_rng(self, host_z: bool):
         """Draw the per-step CPU-RNG quantities in reference order, and with ``host_z`` z and the known-region xi too: the
-        "fixed" xi, then for each position p = npos..1 z (where the solver draws one), the "fresh" xi (p > 1), the
-        shortcut row(s).  ValueError, nothing drawn: ``host_z`` on a sampler built without the host tables."""
+        "fixed" xi, then for each position p = npos..1 z (where the solver draws one), the "fresh" xi (where the position
+        lands on a timestep >= 1), the zeta of a position program's forward jump (where it jumps), the shortcut row(s).
+        ValueError, nothing drawn: ``host_z`` on a sampler built without the host tables."""
         if host_z and self.z_source != "host":
             raise ValueError('prepare_rng(host_z=True) needs a sampler built with z_source="host"')
         draw = lambda: torch.randn(self.n, 1, self.H, self.H)
@@ -492,8 +677,10 @@ class GraphSampler:
         for p in range(self.npos, 0, -1):
             if host_z and self._draws_host_z(p):
                 zs.append(draw())
-            if host_z and self.inpaint == "fresh" and p > 1:
+            if host_z and self.inpaint == "fresh" and self._lands_above_zero(p):
                 xis.append(draw())
+            if host_z and self._jumps(p):
+                self.zeta_table[self.npos - p].copy_(draw().reshape(-1))
             rows.append(_draw_shortcut_row(self.model.n_feat, self.sets))
         self.sc_table.copy_(torch.stack(rows))
         for table, drawn in ((self.z_table, zs), (self.xi_table, xis)):
@@ -575,19 +762,64 @@ class _StridedSampler(GraphSampler):
     """GraphSampler over the subsequence ``taus`` (:func:`timestep_subsequence`) of the T timesteps: the device counter
     holds the position p = S..1 and ``cdm_sample_prologue_sub`` turns it into the timestep tau_p the network sees.  A
     solver subclass validates its tables before this constructor allocates anything, and defines ``_update`` and
-    ``_draws_host_z``.  Snapshots follow the reference's rule on positions: ``snapshot_slots(S, save_rate)``."""
+    ``_draws_host_z``.  Snapshots follow the reference's rule on positions: ``snapshot_slots(S, save_rate)``.
+
+    With a ``program`` (:func:`resample_program`: resampling jumps and / or a late start; None is the plain walk above,
+    which launches exactly what it launched before programs existed) the run has P = program.P positions and everything
+    sized or indexed by the position goes by P: the counter, the per-position tables of the solver, ``sc_table``, the z,
+    zeta and xi tables, ``snapshot_slots(P, save_rate)``.  The prologue reads the program's ``from_t``; after the update,
+    ``cdm_mask_blend_jump`` blends at the level ``land_t[p]`` (when the sampler has a mask) and re-noises the state
+    forward where the position jumps, one launch for both; it is not launched when the program has neither a mask nor a
+    jump (an unmasked late start).  Device noise is keyed by the position, each kind in a key domain of its own, so two
+    visits to one timestep draw different z, xi and zeta.  Host zeta: one randn(n, 1, H, H) at each jumping position,
+    after its z and "fresh" xi and before its shortcut row(s)."""
 
     def __init__(self, model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
-                 use_graph, inpaint, mask_n):
+                 use_graph, inpaint, mask_n, program: Optional[Program] = None):
         self.taus, self.S = taus, len(taus)
+        self.program = program
+        if program is not None and model.in_channels != 1:
+            raise ValueError("resampling and late start are single-channel, like masked sampling: the model has "
+                             f"in_channels = {model.in_channels}")
+        if program is not None and program.P > sched.T:
+            raise ValueError(f"the program has {program.P} positions, more than the T = {sched.T} timesteps the step "
+                             "prologue serves: lower resample, raise jump or take fewer steps")
         super().__init__(model, sched, n, guide_w, params, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, positions=self.S, inpaint=inpaint, mask_n=mask_n)
-        self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=self.dev)
+                         use_graph, positions=self.S if program is None else program.P, inpaint=inpaint, mask_n=mask_n)
         self.cur_k = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.zeta_table = None
+        if program is None:
+            self.steps_t = torch.tensor([0] + self.taus, dtype=torch.int32, device=self.dev)
+            return
+        dv = lambda v: torch.from_numpy(v).to(self.dev)       # noqa: E731
+        self.steps_t, self.land_t, self.fa, self.fb = dv(program.from_t), dv(program.land_t), dv(program.fa), dv(program.fb)
+        self.any_jump = bool((program.up_t != program.land_t).any())
+        if self.any_jump and z_source == "host":
+            self.zeta_table = torch.zeros(max(self.npos - 1, 1), n * self.H * self.H, device=self.dev)
+
+    def _lands_above_zero(self, p):
+        return p > 1 if self.program is None else int(self.program.land_t[p]) >= 1
+
+    def _jumps(self, p):
+        return self.program is not None and int(self.program.up_t[p]) != int(self.program.land_t[p])
 
     def _prologue(self, s):
-        lib().cdm_sample_prologue_sub(_p(self.ctr), self.S, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
+        lib().cdm_sample_prologue_sub(_p(self.ctr), self.npos, self.T, _p(self.steps_t), _p(self.cur_i), _p(self.cur_k),
                                       _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+
+    def _blend(self, s):
+        if self.program is None:
+            return super()._blend(s)
+        if self.inpaint is None and not self.any_jump:
+            return
+        numel = self.n * self.H * self.H
+        ip = self.inpaint is not None
+        lib().cdm_mask_blend_jump(_p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel,
+                                  _p(self.known) if ip else None, _p(self.mask) if ip else None,
+                                  self.mask.numel() if ip else 0, _p(self.cur_k), _p(self.land_t), self.npos, self.T,
+                                  _p(self.ksab) if ip else None, _p(self.ksomab) if ip else None, _p(self.fa),
+                                  _p(self.fb), _p(self.xi_table), numel, 1 if self.inpaint == "fresh" else 0,
+                                  _p(self.zeta_table), numel, self.seed, _p(self.zseed), _p(self.slot), _p(self.snaps), s)
 
 
 class DDIMSampler(_StridedSampler):
@@ -601,23 +833,38 @@ class DDIMSampler(_StridedSampler):
 
     Masked sampling (``inpaint``, ``mask_n``: see :class:`GraphSampler`) blends after every position, at the noise level
     of tau_{p-1}.  Host xi: "fixed", one randn(n, 1, H, H) before the loop over the positions; "fresh", for p = S..2 one
-    after that position's z (if any) and before its shortcut row(s)."""
+    after that position's z (if any) and before its shortcut row(s).
+
+    ``resample`` / ``jump`` / ``t_start`` other than 1 / 1 / None run the position program of :func:`resample_program`
+    (:class:`_StridedSampler`): tables from :func:`ddim_tables_from_pairs`, and ``cdm_ddim_step_pos``, whose device z is
+    keyed by the position, since a program visits one timestep more than once."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  steps=50, eta: float = 0.0, spacing="uniform", save_rate: int = 20, z_source: str = "device",
                  steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
-                 inpaint: Optional[str] = None, mask_n: Optional[int] = None):
+                 inpaint: Optional[str] = None, mask_n: Optional[int] = None, resample: int = 1, jump: int = 1,
+                 t_start: Optional[int] = None):
         taus = timestep_subsequence(sched.T, steps, spacing)
         self.eta = float(eta)
-        tables = ddim_tables(sched.ab_t, taus, self.eta)                   # validates eta before anything is allocated
+        prog = _program(sched.ab_t, taus, resample, jump, t_start, inpaint)
+        if prog is None:
+            tables = ddim_tables(sched.ab_t, taus, self.eta)               # validates eta before anything is allocated
+        else:
+            tables = ddim_tables_from_pairs(sched.ab_t, prog.from_t, prog.land_t, self.eta)
         super().__init__(model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, inpaint, mask_n)
+                         use_graph, inpaint, mask_n, prog)
         self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(self.dev) for v in tables)
 
     def _draws_host_z(self, p):
         return self.eta > 0 and p > 1
 
     def _update(self, s, eps, numel):
+        if self.program is not None:                         # z keyed by the position: a timestep may be visited twice
+            lib().cdm_ddim_step_pos(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                                    1 if self.cfg else 0, self.guide_w, _p(self.cur_k), _p(self.cx), _p(self.ce),
+                                    _p(self.sigma), self.npos, _p(self.z_table), numel, self.seed, _p(self.zseed),
+                                    _p(self.slot), _p(self.snaps), s)
+            return
         lib().cdm_ddim_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
                             1 if self.cfg else 0, self.guide_w, _p(self.cur_i), _p(self.cur_k), _p(self.cx), _p(self.ce),
                             _p(self.sigma), self.S, _p(self.z_table), numel, self.seed, _p(self.zseed), _p(self.slot),
@@ -639,17 +886,26 @@ class DPMSolverSampler(_StridedSampler):
     blended state enters the next position as x_i.  Use "fixed": noise re-drawn at every step ("fresh") breaks the
     smoothness along the trajectory that the second-order combination relies on.  The known-region xi is the one
     quantity that depends on ``z_source`` here.  Host xi: "fixed", one randn(n, 1, H, H) before the loop over the
-    positions; "fresh", for p = S..2 one before that position's shortcut row(s)."""
+    positions; "fresh", for p = S..2 one before that position's shortcut row(s).
+
+    ``resample`` / ``jump`` / ``t_start`` other than 1 / 1 / None run the position program of :func:`resample_program`
+    (:class:`_StridedSampler`) with the tables of :func:`dpmpp_tables_from_pairs`: the position after a forward jump is
+    first order (c1 = 0, ``dprev`` not read), as the first one is."""
 
     def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
                  steps=20, order: int = 2, spacing="uniform", save_rate: int = 20, z_source: str = "device",
                  steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
-                 inpaint: Optional[str] = None, mask_n: Optional[int] = None):
+                 inpaint: Optional[str] = None, mask_n: Optional[int] = None, resample: int = 1, jump: int = 1,
+                 t_start: Optional[int] = None):
         taus = timestep_subsequence(sched.T, steps, spacing)
-        tables = dpmpp_tables(sched.ab_t, taus, order)                    # validates order before anything is allocated
+        prog = _program(sched.ab_t, taus, resample, jump, t_start, inpaint)
+        if prog is None:
+            tables = dpmpp_tables(sched.ab_t, taus, order)                # validates order before anything is allocated
+        else:                                                # the history is dropped after a jump: c1 = 0 there
+            tables = dpmpp_tables_from_pairs(sched.ab_t, prog.from_t, prog.land_t, prog.up_t, order)
         self.order = int(order)
         super().__init__(model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
-                         use_graph, inpaint, mask_n)
+                         use_graph, inpaint, mask_n, prog)
         self.tables = tuple(torch.from_numpy(v).to(self.dev) for v in tables)  # sq, ra, c0, c1, cx, cd
         self.dprev = torch.empty(n * self.H * self.H, device=self.dev)
 
@@ -658,8 +914,11 @@ class DPMSolverSampler(_StridedSampler):
 
     def _update(self, s, eps, numel):
         lib().cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
-                             1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.S,
+                             1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.npos,
                              _p(self.dprev), _p(self.slot), _p(self.snaps), s)
+
+
+PLAIN = (1, 1, None)          # (resample, jump, t_start) of the plain walk: no position program
 
 
 class DDPM:
@@ -683,11 +942,12 @@ class DDPM:
     def denoise_add_noise(self, x, t, pred_noise, z=None):
         return denoise_add_noise(x, t, pred_noise, z, self.sched)
 
-    def _sampler(self, n, guide_w, params, save_rate, solver=None, inpaint=None):
+    def _sampler(self, n, guide_w, params, save_rate, solver=None, inpaint=None, prog=PLAIN):
         """The cached sampler of a configuration.  ``solver``: None, the ancestral GraphSampler, or (sampler class, steps,
         eta or order, spacing) of a strided one; ``inpaint = (known_noise, mask batch extent)`` the masked form of any of
         them (a trailing tagged entry of the key: the contents of known / mask are not part of it, one sampler and one
-        captured graph serve them all)."""
+        captured graph serve them all); ``prog = (resample, jump, t_start)`` of a strided one, a further tagged entry
+        unless it is the plain walk (1, 1, None), whose key and sampler are those of a call without the three."""
         key = (n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, self.z_source)
         cls, sargs = GraphSampler, ()
         if solver is not None:
@@ -698,6 +958,9 @@ class DDPM:
         if inpaint is not None:
             key += (("inpaint",) + tuple(inpaint),)
             ip = dict(inpaint=inpaint[0], mask_n=inpaint[1])
+        if tuple(prog) != PLAIN:
+            key += (("program",) + tuple(prog),)
+            ip.update(resample=prog[0], jump=prog[1], t_start=prog[2])
         smp = self._samplers.get(key)
         if smp is None:
             smp = self._samplers[key] = cls(self.model, self.sched, n, guide_w, params, *sargs, save_rate, self.z_source,
@@ -707,20 +970,30 @@ class DDPM:
         return smp
 
     @torch.no_grad()
-    def _sample(self, solver, x_T, size, params, guide_w, save_rate, known, mask, known_noise):
+    def _sample(self, solver, x_T, size, params, guide_w, save_rate, known, mask, known_noise, prog=PLAIN):
         """Every sample_* method.  ``x_T``: the noise images, or their number to draw them [n,1,size,size], and random
         ``params`` when none are given, from the CPU RNG as the reference does.  The masked-sampling inputs are validated
-        before anything is drawn, so a ValueError leaves the CPU RNG where it was."""
+        before anything is drawn, so a ValueError leaves the CPU RNG where it was; so is ``prog`` = (resample, jump,
+        t_start), the position program of a strided sampler (:func:`resample_program`)."""
         draw = not torch.is_tensor(x_T)
         assert not draw or size == self.model.h
         n = x_T if draw else x_T.shape[0]
         known, mask = check_inpaint(known, mask, n, self.model.h, known_noise, self.model.in_channels)
+        if tuple(prog) != PLAIN:
+            if solver is None:
+                raise ValueError('resample, jump and t_start need a strided sampler: the ancestral one has no position '
+                                 'program; its update is sampler="ddim", eta=1.0 on all T steps')
+            if self.model.in_channels != 1:
+                raise ValueError("resampling and late start are single-channel, like masked sampling: the model has "
+                                 f"in_channels = {self.model.in_channels}")
+            _program(self.sched.ab_t, timestep_subsequence(self.T, solver[1], solver[3]), *prog,
+                     None if known is None else known_noise)
         if draw:
             x_T = torch.randn(n, 1, size, size)
             if params is None:
                 params = torch.rand(n, self.n_cfeat)
         smp = self._sampler(n, guide_w, params, save_rate, solver,
-                            None if known is None else (known_noise, int(mask.shape[0])))
+                            None if known is None else (known_noise, int(mask.shape[0])), prog)
         smp.prepare_rng(host_z=self.z_source == "host")
         return smp.run(x_T, known=known, mask=mask)
 
@@ -739,46 +1012,59 @@ class DDPM:
         return self._sample(None, noise_images, None, params, guide_w, save_rate, known, mask, known_noise)
 
     def sample_ddim(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=50, eta=0.0,
-                    spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
+                    spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed", resample=1, jump=1,
+                    t_start=None):
         """sample_ddpm on ``steps`` of the T timesteps (:class:`DDIMSampler`; ``spacing``: "uniform", "quadratic" or an
         explicit increasing timestep list ending at T, then ``steps`` may be None) -> (samples, intermediate).  x_T and
         random params consume the CPU RNG as sample_ddpm does; eta = 0 is deterministic given x_T and the shortcut
         draws, eta = 1 has the ancestral sampler's variance.  Snapshots: snapshot_slots(steps, save_rate) on positions.
-        ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm`."""
+        ``known`` / ``mask`` / ``known_noise``: masked sampling, as in :meth:`sample_ddpm`.  ``resample`` = R, ``jump`` = J
+        and ``t_start`` (keyword only) run the position program of :func:`resample_program` instead of the plain walk:
+        RePaint's resampling (R > 1 needs known / mask; the run then makes (R - 1) J (S' // J - 1) more network
+        evaluations) and / or a start from the largest timestep <= t_start, where the first argument is the state at that
+        level (:meth:`refine` builds one); snapshots then go by snapshot_slots(P, save_rate).  All three at their
+        defaults is the call without them."""
         return self._sample((DDIMSampler, steps, float(eta), spacing), n_sample, size, params, guide_w, save_rate, known,
-                            mask, known_noise)
+                            mask, known_noise, (resample, jump, t_start))
 
     def sample_ddim_from_noise(self, noise_images, params=None, steps=50, eta=0.0, spacing="uniform", save_rate=20,
-                               guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
+                               guide_w=0.0, *, known=None, mask=None, known_noise="fixed", resample=1, jump=1,
+                               t_start=None):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_ddim`)."""
         return self._sample((DDIMSampler, steps, float(eta), spacing), noise_images, None, params, guide_w, save_rate,
-                            known, mask, known_noise)
+                            known, mask, known_noise, (resample, jump, t_start))
 
     def sample_dpm(self, n_sample=1, size=64, device=None, params=None, guide_w=0.0, steps=20, order=2,
-                   spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed"):
+                   spacing="uniform", save_rate=20, *, known=None, mask=None, known_noise="fixed", resample=1, jump=1,
+                   t_start=None):
         """sample_ddpm on ``steps`` of the T timesteps with the second-order multistep update (:class:`DPMSolverSampler`;
         ``order=1``: first order throughout; ``spacing`` as in :meth:`sample_ddim`) -> (samples, intermediate).  x_T and
         random params consume the CPU RNG as sample_ddpm does; the run is deterministic given x_T and the shortcut
         draws.  Snapshots: snapshot_slots(steps, save_rate) on positions.  ``known`` / ``mask`` / ``known_noise``:
-        masked sampling, as in :meth:`sample_ddpm` (keep "fixed" here, see :class:`DPMSolverSampler`)."""
+        masked sampling, as in :meth:`sample_ddpm` (keep "fixed" here, see :class:`DPMSolverSampler`).  ``resample`` /
+        ``jump`` / ``t_start``: the position program, as in :meth:`sample_ddim`; the multistep history is dropped after
+        every jump (:func:`dpmpp_tables_from_pairs`)."""
         return self._sample((DPMSolverSampler, steps, order, spacing), n_sample, size, params, guide_w, save_rate, known,
-                            mask, known_noise)
+                            mask, known_noise, (resample, jump, t_start))
 
     def sample_dpm_from_noise(self, noise_images, params=None, steps=20, order=2, spacing="uniform", save_rate=20,
-                              guide_w=0.0, *, known=None, mask=None, known_noise="fixed"):
+                              guide_w=0.0, *, known=None, mask=None, known_noise="fixed", resample=1, jump=1,
+                              t_start=None):
         """sample_ddpm_from_noise on ``steps`` of the T timesteps (see :meth:`sample_dpm`)."""
         return self._sample((DPMSolverSampler, steps, order, spacing), noise_images, None, params, guide_w, save_rate,
-                            known, mask, known_noise)
+                            known, mask, known_noise, (resample, jump, t_start))
 
     def inpaint(self, known, mask, params=None, guide_w=0.0, sampler="ddpm", **sampler_kwargs):
         """Complete the maps ``known`` [n,1,H,H] where ``mask`` [n or 1,1,H,H] is 0 -> (samples, intermediate).
 
         ``sampler``: "ddpm" (:meth:`sample_ddpm`), "ddim" (:meth:`sample_ddim`) or "dpmpp" (:meth:`sample_dpm`); x_T and
         random params are drawn as that method draws them, and ``sampler_kwargs`` are its keywords (steps, eta, order,
-        spacing, save_rate, known_noise)."""
+        spacing, save_rate, known_noise; for "ddim" and "dpmpp" also resample, jump, t_start: with any of those "ddpm"
+        raises ValueError)."""
         fns = {"ddpm": self.sample_ddpm, "ddim": self.sample_ddim, "dpmpp": self.sample_dpm}
         if sampler not in fns:
             raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', got {sampler!r}")
+        self._no_program_on_ddpm(sampler, sampler_kwargs)
         if known is None or mask is None:
             raise ValueError("masked sampling needs both known and mask")
         known = torch.as_tensor(known)
@@ -786,6 +1072,47 @@ class DDPM:
             raise ValueError(f"known must have shape [n, 1, H, H], got {tuple(known.shape)}")
         return fns[sampler](known.shape[0], self.model.h, None, params, guide_w, known=known, mask=mask,
                             **sampler_kwargs)
+
+    @staticmethod
+    def _no_program_on_ddpm(sampler, kw):
+        if sampler == "ddpm" and any(k in kw for k in ("resample", "jump", "t_start")):
+            raise ValueError('sampler="ddpm" takes no resample, jump or t_start: the ancestral sampler has no position '
+                             'program; use sampler="ddim", eta=1.0 (its update on the timesteps you choose)')
+
+    @torch.no_grad()
+    def refine(self, init, t_start, params=None, guide_w=0.0, sampler="ddim", noise=None, known=None, mask=None,
+               **sampler_kwargs):
+        """Late start (SDEdit): noise the maps ``init`` [n,1,H,H] to the level t0, the largest timestep of the run that is
+        <= ``t_start``, and denoise from there -> (samples, intermediate).  A small t_start re-draws only the small scales
+        of ``init``; with ``known`` / ``mask`` the run also inpaints, staying close to ``init`` where it generates.
+
+        The start state is sab[t0] init + somab[t0] noise with :func:`known_tables`' fp32 tables (the sampler's noise
+        convention), two products and one sum in fp32 on the device; ``noise`` [n,1,H,H] is drawn from the CPU RNG when
+        None, as the sample_* methods draw x_T.  ``sampler``: "ddim" (:meth:`sample_ddim_from_noise`) or "dpmpp"
+        (:meth:`sample_dpm_from_noise`), with ``sampler_kwargs`` its keywords (steps, eta or order, spacing, save_rate,
+        known_noise, resample, jump).  ValueError: "ddpm" (no position program) or an unknown sampler, ``init`` not
+        [n,1,H,H], ``noise`` of another shape, and what the method raises, all before anything is drawn."""
+        fns = {"ddim": (self.sample_ddim_from_noise, 50), "dpmpp": (self.sample_dpm_from_noise, 20)}
+        self._no_program_on_ddpm(sampler, {"t_start": t_start})
+        if sampler not in fns:
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
+        fn, steps = fns[sampler]
+        H = self.model.h
+        init = torch.as_tensor(init)
+        if tuple(init.shape[1:]) != (1, H, H) or init.dim() != 4:
+            raise ValueError(f"init must have shape [n, 1, {H}, {H}], got {tuple(init.shape)}")
+        if noise is not None and tuple(torch.as_tensor(noise).shape) != tuple(init.shape):
+            raise ValueError(f"noise must have the shape of init, {tuple(init.shape)}")
+        taus = timestep_subsequence(self.T, sampler_kwargs.get("steps", steps), sampler_kwargs.get("spacing", "uniform"))
+        t0 = int(resample_program(self.sched.ab_t, taus, t_start=t_start).from_t[-1])
+        check_inpaint(known, mask, init.shape[0], H, sampler_kwargs.get("known_noise", "fixed"), self.model.in_channels)
+        if noise is None:
+            noise = torch.randn(init.shape)
+        sab, somab = (torch.from_numpy(v) for v in known_tables(self.sched.ab_t))
+        dev = self.sched.ab_t.device
+        a, b = sab[t0].to(dev), somab[t0].to(dev)
+        x = a * init.to(dev, torch.float32) + b * torch.as_tensor(noise).to(dev, torch.float32)
+        return fn(x, params, guide_w=guide_w, known=known, mask=mask, t_start=t_start, **sampler_kwargs)
 
 
 @torch.no_grad()

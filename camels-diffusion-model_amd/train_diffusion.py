@@ -44,6 +44,13 @@ Training for guided sampling (all off by default; without them the outputs are t
                  after the sampling above, complete the --n-samples maps of the first file where the mask of the second
                  is 0 (masked sampling with the sampler the flags above select; arrays [n,H,W] or [n,1,H,W], the mask
                  also [H,W]; 1 = keep the pixel) and write inpainted_samples.npy; the log gets an "Inpainting" line.
+  --inpaint-resample R --inpaint-jump J
+                 with the two inpaint files and --sample-steps: RePaint's resampling, each jump point of the walk
+                 (every J positions) re-noised J positions back and re-denoised R - 1 times; the "Inpainting" line
+                 then names resample=R, jump=J and the number of positions run.
+  --refine-init PATH.npy --refine-t-start T0
+                 with --sample-steps: noise the --n-samples maps of the file to the level of the largest sampled
+                 timestep <= T0 and denoise from there (late start); writes refined_samples.npy and a "Refinement" line.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -87,6 +94,18 @@ def load_inpaint(known_path, mask_path, n, H):
     return check_inpaint(known, mask, n, H)
 
 
+def load_maps(path, n, H):
+    """The --refine-init file as an fp32 tensor [n,1,H,H].  ValueError for another shape or non-finite values."""
+    v = np.load(path, allow_pickle=False)
+    if v.ndim == 4 and v.shape[1] == 1:
+        v = v[:, 0]
+    if v.shape != (n, H, H):
+        raise ValueError(f"the file has shape {v.shape}: expected [{n}, {H}, {H}] or [{n}, 1, {H}, {H}]")
+    if not np.issubdtype(v.dtype, np.floating) or not np.isfinite(v).all():
+        raise ValueError("the maps must be finite floating-point numbers")
+    return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))[:, None]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("lr", type=float)
@@ -124,6 +143,13 @@ def main(argv=None):
                     help="mask [n,H,W], [n,1,H,W] or [H,W] in [0, 1]: 1 = keep the pixel of --inpaint-known, 0 = generate")
     ap.add_argument("--inpaint-noise", choices=["fixed", "fresh"], default="fixed",
                     help="known-region noise: one draw for the run, or one per step")
+    ap.add_argument("--inpaint-resample", type=int, default=1, metavar="R",
+                    help="RePaint resampling: visit every jump point R times (needs the inpaint files and --sample-steps)")
+    ap.add_argument("--inpaint-jump", type=int, default=1, metavar="J", help="jump length of --inpaint-resample, in positions")
+    ap.add_argument("--refine-init", default=None, metavar="PATH.npy",
+                    help="maps [n,H,W] or [n,1,H,W] (normalised data units) to re-draw from --refine-t-start; n = --n-samples")
+    ap.add_argument("--refine-t-start", type=int, default=None, metavar="T0",
+                    help="the timestep --refine-init is noised to (the largest sampled timestep <= T0)")
     a = ap.parse_args(argv)
     if (a.inpaint_known is None) != (a.inpaint_mask is None):
         ap.error("--inpaint-known and --inpaint-mask go together")
@@ -133,6 +159,20 @@ def main(argv=None):
             a.inpaint = load_inpaint(a.inpaint_known, a.inpaint_mask, a.n_samples, a.height)
         except (OSError, ValueError) as e:
             ap.error(f"--inpaint-known / --inpaint-mask: {e}")
+    if (a.inpaint_resample != 1 or a.inpaint_jump != 1) and (a.inpaint is None or a.sample_steps == 0):
+        ap.error("--inpaint-resample / --inpaint-jump need --inpaint-known, --inpaint-mask and --sample-steps S")
+    if a.inpaint_resample < 1 or a.inpaint_jump < 1:
+        ap.error("--inpaint-resample and --inpaint-jump must be >= 1")
+    if (a.refine_init is None) != (a.refine_t_start is None):
+        ap.error("--refine-init and --refine-t-start go together")
+    a.refine = None
+    if a.refine_init is not None:
+        if a.sample_steps == 0:
+            ap.error("--refine-init needs --sample-steps S (the ancestral sampler has no late start)")
+        try:
+            a.refine = load_maps(a.refine_init, a.n_samples, a.height)
+        except (OSError, ValueError) as e:
+            ap.error(f"--refine-init: {e}")
     if a.sample_steps < 0 or a.sample_steps > a.timesteps:
         ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
     if a.clip_grad is not None and not a.clip_grad > 0:
@@ -324,6 +364,12 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
     if a.inpaint is not None:
         known, mask = a.inpaint
         ipk = dict(known=known, mask=mask, known_noise=a.inpaint_noise)
+        rs = ""
+        if (a.inpaint_resample, a.inpaint_jump) != (1, 1):
+            ipk.update(resample=a.inpaint_resample, jump=a.inpaint_jump)
+            taus = cdm_amd.timestep_subsequence(a.timesteps, a.sample_steps, a.spacing)
+            npos = cdm_amd.resample_program(d.sched.ab_t, taus, a.inpaint_jump, a.inpaint_resample).P
+            rs = f", resample={a.inpaint_resample}, jump={a.inpaint_jump}, {npos} positions"
         x_T = torch.randn(ns, 1, H, H)                       # CPU RNG, as the sample_* methods draw it
         t0 = time.time()
         if dpm:
@@ -336,7 +382,15 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
         dt = time.time() - t0
         np.save(os.path.join(out_dir, "inpainted_samples.npy"), filled.cpu().numpy())
         log.write(f"Inpainting {ns} maps (w={a.guide_w}, {float(mask.mean()):.3f} of the pixels known, "
-                  f"{a.inpaint_noise} noise), {how}: {dt:.2f} s\n")
+                  f"{a.inpaint_noise} noise{rs}), {how}: {dt:.2f} s\n")
+    if a.refine is not None:
+        t0 = time.time()
+        kw = dict(dpm) if dpm else dict(ddim)
+        refined, _ = d.refine(a.refine, a.refine_t_start, p, a.guide_w, sampler="dpmpp" if dpm else "ddim", **kw)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        np.save(os.path.join(out_dir, "refined_samples.npy"), refined.cpu().numpy())
+        log.write(f"Refinement of {ns} maps from t_start={a.refine_t_start} (w={a.guide_w}), {how}: {dt:.2f} s\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

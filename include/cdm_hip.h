@@ -450,6 +450,34 @@ int cdm_mask_blend(float* x, float* x2, long long numel, const float* known, con
                    const int* cur_i, const int* cur_k, const int* steps, int npos, int T, const float* sab,
                    const float* somab, const float* xi_table, long long xistride, int fresh, unsigned long long seed,
                    const long long* seed_dev, const int* snap_slot, float* snaps, void* stream);
+/* position programs (resampling, late start): a run of npos positions that may visit one timestep several times.  The
+ * prologue is cdm_sample_prologue_sub with steps = the program's network timesteps (it reads only steps[k]), the update
+ * cdm_ddim_step_pos or cdm_dpmpp_step with tables built per position, then cdm_mask_blend_jump.
+ * cdm_ddim_step_pos is cdm_ddim_step with the device z keyed by the position: Philox under (seed ^ *seed_dev) ^ a fixed
+ * constant of its own, stream k = *cur_k, so two visits to one timestep draw different z; the host z is row npos - k as
+ * there.  hipErrorInvalidValue, nothing launched: a required pointer null, npos < 1, numel <= 0, zstride < 0, snap_slot
+ * without snaps. */
+int cdm_ddim_step_pos(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                      const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
+                      const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
+                      const int* snap_slot, float* snaps, void* stream);
+/* The blend of cdm_mask_blend at the level j = land_t[p] of the position p = *cur_k (land_t, fa, fb [npos + 1], by
+ * position), then the forward jump, with separate fp32 roundings:
+ *   v = the blend of x at j (cdm_mask_blend's arithmetic and m == 0 / m == 1 / j == 0 rules); mask null: v = x, and
+ *       known / sab / somab are not read
+ *   snapshot slot snap_slot[p] <- v
+ *   x <- fa[p] v + fb[p] zeta  where fb[p] != 0, for every pixel, known ones included;  x <- v  where fb[p] == 0
+ * xi: row (fresh ? npos - p : 0) of xi_table, else Philox in cdm_mask_blend's key domain, stream (fresh ? p : 0).
+ * zeta: row npos - p of zeta_table at stride zetastride, else Philox keyed by (seed ^ *seed_dev) ^ a third constant,
+ * stream p; neither read nor drawn where fb[p] == 0.  Writes x (and both halves of x2 when given; x2 may alias x).  A p
+ * outside 1..npos, or a j outside 0..T, writes nothing.  hipErrorInvalidValue, nothing launched: numel <= 0, x / cur_k /
+ * land_t / fa / fb null, npos < 1, T < 1, a negative stride, snap_slot without snaps, and with a mask: known / sab /
+ * somab null, mask_numel <= 0, numel % mask_numel != 0. */
+int cdm_mask_blend_jump(float* x, float* x2, long long numel, const float* known, const float* mask, long long mask_numel,
+                        const int* cur_k, const int* land_t, int npos, int T, const float* sab, const float* somab,
+                        const float* fa, const float* fb, const float* xi_table, long long xistride, int fresh,
+                        const float* zeta_table, long long zetastride, unsigned long long seed,
+                        const long long* seed_dev, const int* snap_slot, float* snaps, void* stream);
 /* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
