@@ -5,6 +5,7 @@ Drop-in for the reference's ContextUnet module API (ContextUnet.py), its diffusi
 repo-root ``cdm_amd.py`` shim maps the hyphenated directory to that name).
 """
 from ._lib import lib  # noqa: F401
+from .augment import augment_maps, augment_source_index, check_augment_ops, draw_augment_ops  # noqa: F401
 from .diffusion import (DDPM, DDIMSampler, DPMSolverSampler, GraphSampler, Program, Schedule,  # noqa: F401
                         check_inpaint, ddim_tables, ddim_tables_from_pairs, denoise_add_noise, dpmpp_tables,
                         dpmpp_tables_from_pairs, known_tables, perturb_input, resample_program, sample_ddpm,
@@ -23,4 +24,5 @@ __all__ = ["ContextUnet", "EmbedFC", "ResidualConvBlock", "UnetDown", "UnetUp", 
            "Schedule", "denoise_add_noise", "perturb_input", "sample_ddpm", "Trainer", "LikelihoodEvaluator",
            "calculate_likelihood", "calculate_elbo_and_bpd", "calculate_elbo_and_bpd_batch",
            "calculate_elbo_and_bpd_dataset", "power_spectrum", "power_spectra", "compare_power_spectra",
-           "calculate_power_spectrum_2d", "compare_distributions", "pdfs"]
+           "calculate_power_spectrum_2d", "compare_distributions", "pdfs", "augment_maps", "draw_augment_ops",
+           "augment_source_index", "check_augment_ops"]

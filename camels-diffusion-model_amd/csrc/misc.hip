@@ -1330,6 +1330,69 @@ __global__ void context_drop_kernel(const float* c, int B, int ncf, float p_drop
     }
 }
 
+// Symmetry augmentation (Trainer(augment=...)): one op per sample, ops[b] = {g, dy, dx}.  g in 0..7: f = g >> 2 flips
+// the columns, then r = g & 3 quarter turns, then a periodic roll by (dy, dx) rows / columns; in torch terms
+//     x = x.flip(-1) if f else x;  x = torch.rot90(x, r, (-2, -1));  x = torch.roll(x, (dy, dx), (-2, -1))
+// A pure gather: output pixel (i, j) is input pixel (i', j').  With n = H - 1, a = (i - dy) mod H, b = (j - dx) mod H:
+//     g   0       1         2           3         4         5       6         7
+//     i'  a       b         n - a       n - b     a         b       n - a     n - b
+//     j'  b       n - a     n - b       a         n - b     a       b         n - a
+// (g = 5 is the transpose, g = 7 the anti-transpose).  Odd r reads the source column-wise.
+//
+// The draw: u = elements 3b, 3b + 1, 3b + 2 of the stream philox_uniform_kernel(out, 3 B, 0, 1, seed, sub, sub_dev)
+// writes; g = min(7, (int)(8 u0)), dy = min(H - 1, (int)(H u1)), dx = min(H - 1, (int)(H u2)) in fp32 (the min: u01 is
+// not promised to stay below 1).  mode bit 0 keeps g, bit 1 keeps dy and dx; the rest is 0, all three are consumed.
+static __device__ __forceinline__ float philox_u01_elem(unsigned long long seed, uint32_t sub, long long e) {
+    const long long q = e >> 2;
+    const U4 r = philox((uint32_t)q, (uint32_t)((unsigned long long)q >> 32), sub, 0x0417u, (uint32_t)seed,
+                        (uint32_t)(seed >> 32));
+    const int j = (int)(e & 3);
+    return u01(j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w)));
+}
+__global__ void augment_draw_kernel(int* ops, int B, int H, int mode, unsigned long long seed, uint32_t sub,
+                                    const int* sub_dev) {
+    if (sub_dev) sub += (uint32_t)*sub_dev;
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+        const float u0 = philox_u01_elem(seed, sub, 3ll * b), u1 = philox_u01_elem(seed, sub, 3ll * b + 1),
+                    u2 = philox_u01_elem(seed, sub, 3ll * b + 2);
+        const int g = min(7, (int)(8.f * u0)), dy = min(H - 1, (int)((float)H * u1)), dx = min(H - 1, (int)((float)H * u2));
+        ops[3 * b] = (mode & 1) ? g : 0;
+        ops[3 * b + 1] = (mode & 2) ? dy : 0;
+        ops[3 * b + 2] = (mode & 2) ? dx : 0;
+    }
+}
+
+// perturb_kernel with the gather folded into the read of x (same expression, same roundings; the noise is not
+// transformed).  noise == NULL: out = the transformed map alone.  An op outside its range is clamped into it.
+__global__ void perturb_aug_kernel(const float* x, const int* ops, const float* noise, const int* t, const int* cur_i,
+                                   long long nstride, const float* sab, const float* omab, int N, int HW, int H, int T,
+                                   float* out, float* tin) {
+#pragma clang fp contract(off)
+    const long long total = (long long)N * HW;
+    const int ci = cur_i ? *cur_i : 0;
+    const float* nz = (noise && cur_i) ? noise + (long long)(T - ci) * nstride : noise;
+    const int nn = H - 1;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int n = (int)(i / HW), p = (int)(i - (long long)n * HW);
+        const int row = p / H, col = p - row * H;
+        const int g = min(7, max(0, ops[3 * n])), dy = min(nn, max(0, ops[3 * n + 1])), dx = min(nn, max(0, ops[3 * n + 2]));
+        int a = row - dy, b = col - dx;
+        a += a < 0 ? H : 0; b += b < 0 ? H : 0;
+        const int r = g & 3;
+        int si = r == 0 ? a : (r == 1 ? b : (r == 2 ? nn - a : nn - b));
+        int sj = r == 0 ? b : (r == 1 ? nn - a : (r == 2 ? nn - b : a));
+        if (g & 4) sj = nn - sj;
+        const float xv = x[(long long)n * HW + (long long)si * H + sj];
+        if (noise) {
+            const int ti = cur_i ? ci : t[n];
+            out[i] = sab[ti] * xv + omab[ti] * nz[i];
+            if (tin && p == 0) tin[n] = (float)ti / (float)T;
+        } else {
+            out[i] = xv;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------------
@@ -1767,6 +1830,21 @@ CDM_API int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsig
         return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(context_drop_kernel, dim3(nblocks((long long)B * ncf)), dim3(256), 0, S(stream), c, B, ncf, p_drop,
                        seed, sub, sub_dev, c_out, keep);
+    return cdm_status();
+}
+CDM_API int cdm_augment_draw(int* ops, int B, int H, int mode, unsigned long long seed, unsigned int sub,
+                             const int* sub_dev, void* stream) {
+    if (!ops || B < 1 || H < 1 || mode < 0 || mode > 3) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(augment_draw_kernel, dim3(nblocks(B)), dim3(256), 0, S(stream), ops, B, H, mode, seed, sub, sub_dev);
+    return cdm_status();
+}
+CDM_API int cdm_perturb_aug(const float* x, const int* ops, const float* noise, const int* t, const int* cur_i,
+                            long long nstride, const float* sab, const float* omab, int N, int HW, int H, int T,
+                            float* out, float* tin, void* stream) {
+    if (!x || !ops || !out || out == x || N < 1 || H < 1 || (long long)H * H != HW) return (int)hipErrorInvalidValue;
+    if (noise && ((!t && !cur_i) || !sab || !omab || T < 1)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(perturb_aug_kernel, dim3(nblocks((long long)N * HW)), dim3(256), 0, S(stream), x, ops, noise, t,
+                       cur_i, nstride, sab, omab, N, HW, H, T, out, tin);
     return cdm_status();
 }
 CDM_API int cdm_pack_conv3x3(const float* W, const float* b, int Cin, int Cout, const float* gamma, const float* beta,

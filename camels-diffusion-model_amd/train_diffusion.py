@@ -34,6 +34,10 @@ Training for guided sampling (all off by default; without them the outputs are t
                  clip the global L2 norm of the gradient to NORM before every Adam update (clip_grad_norm_ semantics,
                  computed on the device inside the captured step; inf: no scaling) and skip a step whose gradient holds
                  a NaN / inf; the epoch line then ends with the last gradient norm and the count of skipped steps.
+  --augment none|d4|shift|d4+shift
+                 train every sample of a step on a random image of itself under the symmetries of the maps: a flip and
+                 quarter turns (d4), a periodic shift (shift) or both, drawn on the device inside the captured step; the
+                 log gets a "Training options" line that names the mode.
   --sample-steps S [--eta E] [--spacing uniform|quadratic]
                  run the sampling at the end on S of the TIMESTEPS with the strided DDIM sampler (eta 0: deterministic)
                  instead of all of them; the log lines then name steps=S, eta=E.
@@ -127,6 +131,8 @@ def main(argv=None):
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep and sample from EMA weights")
     ap.add_argument("--clip-grad", type=float, default=None, metavar="NORM",
                     help="clip the gradient's global L2 norm to NORM; skip steps with a non-finite gradient")
+    ap.add_argument("--augment", choices=["none", "d4", "shift", "d4+shift"], default="none",
+                    help="symmetry augmentation inside the step: flips / quarter turns, periodic shifts, or both")
     ap.add_argument("--resume", default=None, metavar="PATH",
                     help="write trainer_epoch_N.pt checkpoints; continue from PATH if it exists")
     ap.add_argument("--sample-steps", type=int, default=0, metavar="S",
@@ -235,8 +241,12 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     model = ContextUnet(1, a.n_feat, n_cfeat, H).to(dev)
     trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed, ema_decay=a.ema, p_uncond=a.p_uncond,
-                      clip_grad_norm=a.clip_grad)
+                      clip_grad_norm=a.clip_grad, augment=a.augment)
     log = open(os.path.join(out_dir, "timing_and_performance.log"), "a") if rank == 0 else None
+    if rank == 0 and a.augment != "none":      # without the option the log is what it was
+        msg = f"Training options: p_uncond={a.p_uncond:g}, ema={a.ema}, clip_grad={a.clip_grad}, augment={a.augment}"
+        print(msg, flush=True)
+        log.write(msg + "\n")
     loss_log, val_log = [], []
     first_ep = 0
     if a.resume is not None:

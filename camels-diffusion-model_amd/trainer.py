@@ -16,6 +16,8 @@ MI355X design:
     state_dict() / load_state_dict() that continue a run bit-identically;
   * optional, off by default: global-norm gradient clipping and a non-finite step skip (clip_grad_norm), computed on
     the device inside the captured step (see Trainer);
+  * optional, off by default: symmetry augmentation (augment: a random flip / quarter turn and / or periodic shift per
+    sample, drawn from Philox inside the step and folded into the perturb kernel's read of x0; see augment.py);
   * data parallel: one process per GPU; each rank trains on its own shard of the global batch; the
     flat gradient buffer is laid out in backward-completion order and cut into stage buckets that are
     all-reduced (RCCL over xGMI) asynchronously as soon as the engine reports a stage complete, so the
@@ -32,6 +34,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from ._lib import lib
+from .augment import check_augment_ops, check_mode
 from .diffusion import Schedule
 
 STAGES: Tuple[Tuple[str, Tuple[str, ...]], ...] = (
@@ -89,7 +92,8 @@ class GradBucketer:
 class Trainer:
     def __init__(self, model, lrate: float, timesteps: int, batch_size: int, seed: int = 0,
                  use_graph: bool = True, group=None, broadcast_buffers: bool = True, force_ddp: bool = False,
-                 ema_decay: Optional[float] = None, p_uncond: float = 0.0, clip_grad_norm: Optional[float] = None):
+                 ema_decay: Optional[float] = None, p_uncond: float = 0.0, clip_grad_norm: Optional[float] = None,
+                 augment: str = "none"):
         """``force_ddp``: take the data-parallel path (stage-bucketed async all-reduce, rank-0 broadcasts, eager
         steps) even in a one-rank process group — RCCL readiness on a one-GPU box (tests/test_gpu_rccl.py).
         ``ema_decay``: keep ``self.ema``, an exponential moving average of the parameters, updated inside the fused
@@ -108,7 +112,16 @@ class Trainer:
         of the last step's gradient before clipping; ``check_skipped()`` reads the counter (one host sync, per epoch).
         Data parallel: the norm is taken after the last all-reduce, of the summed buffer times 1 / world, the averaged
         gradient Adam sees; every rank holds identical bytes there, so every rank computes the same norm, coefficient
-        and skip decision without another collective."""
+        and skip decision without another collective.
+        ``augment``: ``"none"`` (default) launches exactly the unaugmented step.  ``"d4"``, ``"shift"`` and
+        ``"d4+shift"`` train each sample of a step on a random image of itself under the symmetries of the data (a
+        flip and quarter turns, a periodic roll, or both; augment.py has the definition): the ops [B, 3] come from one
+        more Philox draw keyed by the step counter (``cdm_augment_draw``, sub-stream ``4 << 24``), and
+        ``cdm_perturb_aug`` reads x0 through them in place of ``cdm_perturb``, both inside the captured step.  The
+        noise is not transformed and the caller's batch in ``self.x0`` stays intact.  ``step(aug_ops=...)`` replaces
+        the draw for one step (eager).  Data parallel: the per-rank seed already separates the ranks' draws."""
+        self._aug_mode = check_mode(augment)
+        self.augment = augment
         if clip_grad_norm is not None:
             _check_max_norm(clip_grad_norm)
         if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
@@ -202,6 +215,7 @@ class Trainer:
         self.graph = None
         self.steps = 0
         self._inject = None
+        self._aug_ops = None          # step(aug_ops=...): this step's ops in place of the device draw
         self.stage_hook = None        # optional extra on_stage(name) callback (tests / tracing)
         self.grad_numel = None        # per-step override of the loss-mean count (data-parallel ragged batches)
 
@@ -209,7 +223,7 @@ class Trainer:
     def _use(self, B: int):
         b = self._bufs.get(B)
         if b is None:
-            b = self._bufs[B] = _StepBufs(self.eng, B, self.H, self.ncf, self.dev)
+            b = self._bufs[B] = _StepBufs(self.eng, B, self.H, self.ncf, self.dev, aug=self._aug_mode != 0)
         self.cur = b
         return b
 
@@ -316,6 +330,7 @@ class Trainer:
             "ema_decay": None if self.ema is None else float(self.ema_decay.item()),
             "p_uncond": float(self.p_uncond),
             "clip_grad_norm": float(self.max_norm.item()) if self.clip else None, "skipped": cpu(self.skipped),
+            "augment": self.augment,
         }
 
     def load_state_dict(self, sd: Dict[str, object]):
@@ -329,6 +344,9 @@ class Trainer:
             raise ValueError("the checkpoint clips gradients and the trainer was built with clip_grad_norm=None"
                              if not self.clip else
                              "the trainer clips gradients and the checkpoint was written without clipping")
+        if sd.get("augment", "none") != self.augment:               # checkpoints from before the option: "none"
+            raise ValueError(f"the checkpoint was written with augment={sd.get('augment', 'none')!r} and the trainer "
+                             f"was built with augment={self.augment!r}")
         if list(sd["layout"]) != list(self.offsets):
             raise ValueError("checkpoint holds a different parameter list than this model")
         own = self.model.state_dict()
@@ -386,8 +404,16 @@ class Trainer:
             else:
                 lb.cdm_context_drop(_p(sb.c), B, self.ncf, self.p_uncond, seed, 3 << 24, _p(self.ctr), _p(sb.c_eff),
                                     _p(sb.keep), s)
-        lb.cdm_perturb(_p(sb.x0), _p(sb.noise), _p(sb.t_int), None, 0, _p(self.sched.sab), _p(self.sched.omab), B, HW,
-                       self.T, _p(sb.xpert), _p(sb.t_in), s)
+        if self._aug_mode == 0:
+            lb.cdm_perturb(_p(sb.x0), _p(sb.noise), _p(sb.t_int), None, 0, _p(self.sched.sab), _p(self.sched.omab), B,
+                           HW, self.T, _p(sb.xpert), _p(sb.t_in), s)
+        else:                      # symmetry augmentation: xpert reads x0 through the ops, sb.x0 stays intact
+            if self._aug_ops is not None:
+                sb.ops.copy_(self._aug_ops)
+            else:
+                lb.cdm_augment_draw(_p(sb.ops), B, self.H, self._aug_mode, seed, 4 << 24, _p(self.ctr), s)
+            lb.cdm_perturb_aug(_p(sb.x0), _p(sb.ops), _p(sb.noise), _p(sb.t_int), None, 0, _p(self.sched.sab),
+                               _p(self.sched.omab), B, HW, self.H, self.T, _p(sb.xpert), _p(sb.t_in), s)
         self.eng.repack(P, True, s)
         eps = self.eng.forward(sb.ws, P, sb.xpert, sb.t_in, c_in, self.sc[:nf], self.sc[nf:], B, s)
         gnum = float(B * HW) if self.grad_numel is None else float(self.grad_numel)
@@ -428,7 +454,8 @@ class Trainer:
         self.graph = g
 
     def step(self, x0: Optional[torch.Tensor] = None, c: Optional[torch.Tensor] = None, inject=None,
-             global_count: Optional[int] = None, eager: bool = False) -> torch.Tensor:
+             global_count: Optional[int] = None, eager: bool = False,
+             aug_ops: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One training step on batch (x0 [B,1,H,H] in [0,1], c [B, n_cfeat] or None = unconditional).
 
         ``inject=(noise [B,1,H,H], t [B] int, shortcut [2*n_feat] = weight|bias)`` replaces the on-device
@@ -436,11 +463,18 @@ class Trainer:
         ``keep [B]`` (0 / 1), in place of the context-dropout draw: rows with keep == 0 train on c = 0.
         ``global_count`` (data parallel): the number of samples all ranks process in this step when the ranks'
         batches differ in size; the gradient is then the mean over those samples (each rank weighted by its
-        sample count, F.mse_loss over the union) instead of the mean of per-rank means."""
+        sample count, F.mse_loss over the union) instead of the mean of per-rank means.
+        ``aug_ops`` (a trainer built with ``augment`` other than "none"): an integer tensor [B, 3] of (g, dy, dx) per
+        sample, used in place of the device draw for this step (runs eagerly, like ``inject``; ValueError for what
+        ``check_augment_ops`` rejects)."""
         if self._in_ema:
             raise RuntimeError("Trainer.step inside ema_weights(): the parameters hold the EMA")
-        self._inject = inject
         B = self.B if x0 is None else x0.shape[0]
+        if aug_ops is not None:
+            if self._aug_mode == 0:
+                raise ValueError('aug_ops given to a Trainer built with augment="none"')
+            aug_ops = check_augment_ops(aug_ops, B, self.H)
+        self._inject, self._aug_ops = inject, aug_ops
         HW = self.H * self.H
         self.grad_numel = None if global_count is None else float(global_count) * HW / self.world
         sb = self._use(B)
@@ -453,7 +487,8 @@ class Trainer:
         if self.ddp and self.broadcast_buffers:
             import torch.distributed as dist
             dist.broadcast(self.bnflat, 0, group=self.group)
-        if self.use_graph and inject is None and B == self.B and self.grad_numel is None and not eager:
+        if self.use_graph and inject is None and aug_ops is None and B == self.B and self.grad_numel is None \
+                and not eager:
             if self.graph is None:
                 self._body(_s())          # eager warm-up step (loads every kernel) then capture
                 self._capture()
@@ -517,7 +552,7 @@ def adam_bias_table(beta1: float, beta2: float, n: int = 40960) -> torch.Tensor:
 class _StepBufs:
     """Device buffers of one training step at batch size B (engine workspace included)."""
 
-    def __init__(self, eng, B: int, H: int, ncf: int, dev):
+    def __init__(self, eng, B: int, H: int, ncf: int, dev, aug: bool = False):
         HW = H * H
         self.B = B
         self.x0 = torch.zeros(B, H, H, device=dev)
@@ -529,4 +564,6 @@ class _StepBufs:
         self.deps = torch.empty(B, H, H, device=dev)
         self.c_eff = torch.zeros(B, ncf, device=dev)                 # c after context dropout (p_uncond > 0)
         self.keep = torch.ones(B, dtype=torch.int32, device=dev)     # its mask: 0 = dropped
+        if aug:
+            self.ops = torch.zeros(B, 3, dtype=torch.int32, device=dev)   # (g, dy, dx) per sample (augment != "none")
         self.ws = eng.workspace(B, True)

@@ -538,6 +538,27 @@ int cdm_adam_clipped(float* p, const float* g, float* m, float* v, float* ema, l
  * hipErrorInvalidValue: p_drop outside [0, 1] or NaN, B < 1, ncf < 1, c or c_out null, c_out == c. */
 int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsigned long long seed, unsigned int sub,
                      const int* sub_dev, float* c_out, int* keep, void* stream);
+/* symmetry augmentation of square single-channel maps (Trainer(augment=...)).  An op is {g, dy, dx}: f = g >> 2 flips
+ * the columns, then r = g & 3 quarter turns, then a periodic roll by (dy, dx) rows / columns, i.e. on one [H][H] map
+ *     x = x.flip(-1) if f else x;  x = torch.rot90(x, r, (-2, -1));  x = torch.roll(x, (dy, dx), (-2, -1)).
+ * Output pixel (i, j) is input pixel (i', j'); with n = H - 1, a = (i - dy) mod H, b = (j - dx) mod H:
+ *     g   0   1      2      3      4      5   6      7
+ *     i'  a   b      n - a  n - b  a      b   n - a  n - b
+ *     j'  b   n - a  n - b  a      n - b  a   b      n - a
+ * cdm_augment_draw: ops [B][3].  u = elements 3b, 3b + 1, 3b + 2 of what cdm_philox_uniform(out, 3 B, 0, 1, seed, sub,
+ * sub_dev) writes; g = min(7, (int)(8 u0)), dy = min(H - 1, (int)(H u1)), dx = min(H - 1, (int)(H u2)), in fp32.
+ * mode: 0 none, 1 d4 (g drawn), 2 shift (dy, dx drawn), 3 both; what the mode does not draw is 0, and every mode
+ * consumes all three uniforms.  hipErrorInvalidValue: ops null, B < 1, H < 1, mode outside 0..3. */
+int cdm_augment_draw(int* ops, int B, int H, int mode, unsigned long long seed, unsigned int sub, const int* sub_dev,
+                     void* stream);
+/* cdm_perturb with the gather folded in: out[b][p] = sab[t_b] x[b][src_b(p)] + omab[t_b] noise[b][p] (+ tin), the same
+ * fp32 expression and roundings as cdm_perturb (all-zero ops: its output bit for bit); the noise is not transformed and
+ * there is no intermediate buffer.  noise == NULL: out[b][p] = x[b][src_b(p)] alone (t, cur_i, sab, omab, tin unused).
+ * An op outside its range is clamped into it (callers validate on the host).  hipErrorInvalidValue: x, ops or out
+ * null; out == x; N < 1; H < 1; HW != H * H; with noise: neither t nor cur_i, sab or omab null, T < 1. */
+int cdm_perturb_aug(const float* x, const int* ops, const float* noise, const int* t, const int* cur_i,
+                    long long nstride, const float* sab, const float* omab, int N, int HW, int H, int T, float* out,
+                    float* tin, void* stream);
 /* weight repacking (+ eval-mode BatchNorm folding) */
 /* kc = 0: K order tap-major (k = tap*C + ci); kc = 16: channel-chunk-major (k = ((ci/16)*9 + tap)*16 + ci%16),
  * the order cdm_conv3x3_fwd(kc = 16) consumes (wdg is chunked over Cout).  ConvTranspose packing: */
