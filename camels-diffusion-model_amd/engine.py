@@ -36,6 +36,7 @@ BN_MOM = 0.1
 GN_EPS = 1e-5
 GN_GROUPS = 8
 CHUNK = 128           # pixels per statistics partial (== GEMM M tile)
+WGRAD_BLOCKS = 768    # grid of the kernel-row weight gradient: three whole rounds of 256 CUs (wgrad_splits)
 EPI_RELU, EPI_ACCUM = 1, 2
 APPLY_POOL, APPLY_FILM, APPLY_RESID, APPLY_RELU = 1, 2, 4, 8
 
@@ -64,13 +65,39 @@ def _cdiv(a, b):
 
 
 class LayerSpec:
-    """One Conv3x3 -> BatchNorm2d -> ReLU (diffusion_utilities.py:26-37)."""
+    """One Conv3x3 -> BatchNorm2d -> ReLU (diffusion_utilities.py:26-37) and its place in the U-Net's conv chain.
 
-    def __init__(self, name, cin, cout, S):
-        self.name, self.cin, self.cout, self.S = name, cin, cout, S
+    kind: where its activation goes — "dense": a private z that the next layer reads; "resid" / "pool" / "film" /
+    "plain": through that transform into a slice of a concatenation buffer.  src / dst name workspace buffers as
+    (buffer, first channel, channels), the channels in units of n_feat; None is the z between two consecutive layers
+    (for layer 0 the image).  The gradient of a cat* slice is the same slice of dcat*.
+    src_slot / dst_slot: amax-slot keys of the two operands (h3).  Producers writing slices of one concatenation
+    buffer share that buffer's slot (its consumers read the whole buffer, or a slice whose max the shared slot bounds
+    from above — harmless for the scale).
+    stage: the backward's on_stage name; STAGE_PROBE maps it to the forward's stage_probe point."""
+
+    def __init__(self, index, name, cin, cout, S, stage, kind, src, dst):
+        self.index, self.name, self.cin, self.cout, self.S = index, name, cin, cout, S
+        self.stage, self.kind, self.src, self.dst = stage, kind, src, dst
+        self.prev = self.next = None
+        self.src_slot = src[0] if src else None          # None src: the previous layer's dst_slot (conv_layers)
+        self.dst_slot = dst[0] if dst else "z:" + name
         self.w, self.b = name + ".0.weight", name + ".0.bias"
         self.bn = name + ".1"
         self.kc = conv_kc(cin, cout)
+
+
+class ConvTSpec:
+    """One ConvTranspose2d(cin, n_feat, 2, 2) (diffusion_utilities.py:86): reads the whole concatenation buffer `src`
+    (Hin x Hin), writes `dst`; `consumer` is the conv layer that reads dst, so its dgrad writes the gradient of dst (and
+    records its max in the slot g_slot for the h3 ConvT backward).  src and dst are their own amax-slot keys."""
+
+    def __init__(self, name, stage, src, cin, Hin, dst, consumer):
+        self.name, self.stage, self.src, self.cin, self.Hin, self.dst = name, stage, src, cin, Hin, dst
+        self.consumer, self.g_slot = consumer, "gT:" + consumer.name
+
+
+STAGE_PROBE = {"init": "x0", "down1": "d1", "down2": "d2", "up1": "film2", "up2": "u3"}
 
 
 def conv_kc(cin: int, cout: int) -> int:
@@ -79,20 +106,35 @@ def conv_kc(cin: int, cout: int) -> int:
 
 
 def conv_layers(nf: int, H: int, cin0: int = 1):
-    """The 18 Conv3x3 -> BatchNorm -> ReLU layers in forward order; cin0 = the image channels the init conv reads
-    (in_channels, padded to a multiple of 4 when > 1)."""
+    """The 18 Conv3x3 -> BatchNorm -> ReLU layers in forward order, with the whole wiring of the U-Net's conv chain
+    (LayerSpec); cin0 = the image channels the init conv reads (in_channels, padded to a multiple of 4 when > 1)."""
     L = []
 
-    def rcb(prefix, cin, cout, S):
-        L.append(LayerSpec(prefix + ".conv1", cin, cout, S))
-        L.append(LayerSpec(prefix + ".conv2", cout, cout, S))
+    def rcb(stage, prefix, cin, cout, S, src=None, kind="dense", dst=None):
+        L.append(LayerSpec(len(L), prefix + ".conv1", cin, cout, S, stage, "dense", src, None))
+        L.append(LayerSpec(len(L), prefix + ".conv2", cout, cout, S, stage, kind, None, dst))
 
-    rcb("init_conv", cin0, nf, H)
-    rcb("down1.model.0", nf, nf, H); rcb("down1.model.1", nf, nf, H)
-    rcb("down2.model.0", nf, 2 * nf, H // 2); rcb("down2.model.1", 2 * nf, 2 * nf, H // 2)
-    rcb("up1.model.1", nf, nf, H // 2); rcb("up1.model.2", nf, nf, H // 2)
-    rcb("up2.model.1", nf, nf, H); rcb("up2.model.2", nf, nf, H)
+    rcb("init", "init_conv", cin0, nf, H, kind="resid", dst=("catO", 1, 1))
+    rcb("down1", "down1.model.0", nf, nf, H, src=("catO", 1, 1))
+    rcb("down1", "down1.model.1", nf, nf, H, kind="pool", dst=("catU2", 1, 1))
+    rcb("down2", "down2.model.0", nf, 2 * nf, H // 2, src=("catU2", 1, 1))
+    rcb("down2", "down2.model.1", 2 * nf, 2 * nf, H // 2, kind="pool", dst=("catU1", 2, 2))
+    rcb("up1", "up1.model.1", nf, nf, H // 2, src=("yT1", 0, 1))
+    rcb("up1", "up1.model.2", nf, nf, H // 2, kind="film", dst=("catU2", 0, 1))
+    rcb("up2", "up2.model.1", nf, nf, H, src=("yT2", 0, 1))
+    rcb("up2", "up2.model.2", nf, nf, H, kind="plain", dst=("catO", 0, 1))
+    for a, b in zip(L, L[1:]):
+        a.next, b.prev = b, a
+        if b.src is None:
+            b.src_slot = a.dst_slot
     return L
+
+
+def convT_layers(nf: int, H: int, L):
+    """The two 2x2 ConvT layers in forward order (L = conv_layers(...): each one's consumer)."""
+    reads = {l.src[0]: l for l in L if l.src}
+    return [ConvTSpec("up1.model.0", "up1", "catU1", 4 * nf, H // 4, "yT1", reads["yT1"]),
+            ConvTSpec("up2.model.0", "up2", "catU2", 2 * nf, H // 2, "yT2", reads["yT2"])]
 
 
 # 3x3 conv arithmetic: "fp32" = fp32 MFMA (v_mfma_f32_32x32x2_f32); "x6" = fp32-accurate split-bf16
@@ -130,46 +172,32 @@ class UNetEngine:
         # the 16-bit-MFMA kernel family with every train-mode fusion: h3 (fp32-class) and bf16 (C4 mixed precision)
         self.x16 = self.nterm in (1, NT_H3)
         self.h3 = self.nterm == NT_H3
-        # BatchNorm backward fused into the staging of the layer's dgrad / wgrad (dy never written);
-        # $CDM_FUSE_BN_BWD=0 keeps the separate apply kernel (A/B checks)
+        # BatchNorm backward fused into the staging of the layer's dgrad, which also stores the dy it computes for the
+        # weight gradient (staged there instead of evaluated again in each of its 3 kernel-row blocks).  Under one-term
+        # (bf16) arithmetic dy comes from an elementwise pass of its own (cdm_bn_bwd_dy) and the dgrad runs on the
+        # forward's staging schedule (halo two chunks ahead), for which the BN-backward staging has no room.  The A/B
+        # results that decided both forms: DESIGN.md section 3.3.  $CDM_FUSE_BN_BWD=0 keeps the separate apply kernel
+        # (A/B checks)
         self.fuse_bn_bwd = self.x16 and os.environ.get("CDM_FUSE_BN_BWD", "1") != "0"
         # a dense BatchNorm + ReLU applied inside the next conv's staging ($CDM_FUSE_BN_FWD=0: apply kernel)
         self.fuse_bn_fwd = self.x16 and os.environ.get("CDM_FUSE_BN_FWD", "1") != "0"
-        # a fused layer's dgrad also stores the dy its staging computes (the BN backward of g), and the weight gradient
-        # stages that dy instead of evaluating the BN backward again in each of its 3 kernel-row blocks
-        # ($CDM_DY_STORE=0 / 1; same-box A/B, 2 runs each: C4 29.64-29.89 -> 29.02-29.04 ms per step, C2 50.57-50.62 ->
-        # 50.36-50.37 ms, profiles/r4_ab_dy_store_ks4.txt)
-        self.dy_store = self.x16 and os.environ.get("CDM_DY_STORE", "1") == "1"
         # a fused producer's BN-backward channel sums accumulated in its consumer's weight-gradient X staging (which
         # stages the producer's y anyway), after the consumer's dgrad wrote the producer's g: no separate pass over g and
-        # y.  Round 3 kept it off for h3 (C2 52.56 -> 55.07 ms: the h3 weight gradient with the BN-backward dy staging sat
-        # at the 256-VGPR limit); since round 4 the weight gradient stages the dy the dgrad stored (dy_store) and the
-        # sums fit (250 VGPRs, no spill): same-box A/B, 2 runs each, C2 50.36-50.38 -> 49.39-49.45 ms per step
-        # (profiles/r4_ab_sums_dy_pass.txt).  $CDM_FUSE_BN_SUMS=0 / 1 forces it.
-        env = os.environ.get("CDM_FUSE_BN_SUMS")
-        self.fuse_bn_sums = self.x16 and (env == "1" if env is not None else (self.dy_store or not self.h3))
-        # init_conv.conv1's BN backward inside its weight-gradient kernel ($CDM_FUSE_CIN1_BWD=0: the apply kernel)
-        self.fuse_cin1_bwd = os.environ.get("CDM_FUSE_CIN1_BWD", "1") != "0"
+        # y; the weight gradient stages a stored dy, so the sums fit (250 VGPRs, no spill): same-box A/B, 2 runs each,
+        # C2 50.36-50.38 -> 49.39-49.45 ms per step (profiles/r4_ab_sums_dy_pass.txt).  $CDM_FUSE_BN_SUMS=0: off
+        self.fuse_bn_sums = self.x16 and os.environ.get("CDM_FUSE_BN_SUMS", "1") == "1"
         # C4 mixed precision (bf16 arithmetic, train mode): the fused Conv -> BN -> ReLU chain's pre-norm outputs y and
         # their gradients g are stored as bf16 (torch.autocast keeps conv outputs and their gradients in bf16), halving
         # the bytes every fused conv stages; BN statistics, accumulators, master weights stay fp32.  The chain's ends
         # (concatenation slices, pool / FiLM / residual outputs, the C_in = 1 init conv) stay fp32.
         # $CDM_ACT16=0 keeps fp32 activations (A/B checks).
         self.act16 = self.nterm == 1 and os.environ.get("CDM_ACT16", "1") != "0"
-        # bf16 (one-term) arithmetic: dy of a fused layer by a separate elementwise pass (cdm_bn_bwd_dy) and the
-        # dgrad on the forward's staging schedule (halo two chunks ahead) instead of the BN-backward staging.  Round 4
-        # kept it off (C4 28.20 -> 28.31-28.33 ms: the pass took 213 us per 64^2 layer, profiles/r4_ab_sums_dy_pass.txt);
-        # round 5 loads the pass's per-channel coefficients once per thread instead of per element, and it pays: same-box
-        # A/B, 2 runs each, C4 27.33-27.38 -> 26.86-26.89 ms per step (profiles/r5_ab_dy_pass.txt).  $CDM_DY_PASS=0: off
-        self.dy_pass = self.dy_store and self.nterm == 1 and os.environ.get("CDM_DY_PASS", "1") == "1"
-        # train: out.1's GroupNorm + ReLU inside out.3's forward and weight-gradient staging, zO never written
-        # ($CDM_FUSE_GN_OUT=0: the apply kernel writes zO)
-        self.fuse_gn_out = os.environ.get("CDM_FUSE_GN_OUT", "1") != "0"
         # eval: the pool / FiLM / residual applies in the conv epilogue (fuses_eval)
         self.fuse_eval = self.x16 and os.environ.get("CDM_FUSE_EVAL", "1") != "0"
         self.device = torch.device(device)
         self.layers = conv_layers(n_feat, height, self.cp)
-        self.L = {l.name: l for l in self.layers}
+        self.convT = convT_layers(n_feat, height, self.layers)
+        self.stages = {st: [l for l in self.layers if l.stage == st] for st in STAGE_PROBE}
         self.KK0 = (height // 4) ** 2
         # up0 on large maps (config 5: k = 64, 1.07 G weights): VALU kernels over the weights in their reference layout
         # (cdm_up0_fwd / cdm_up0_wgrad) and one W^T for the input gradient, instead of two 4.3 GB repacks per step
@@ -403,14 +431,9 @@ class UNetEngine:
         """Producer l's train-mode BatchNorm apply (z = relu(y s + t)) runs inside the staging of the next conv (its
         forward and its weight gradient): z is never written.  Needs the LDS-halo path for both convs (max / min
         epilogue on l, BN-ReLU staging on the consumer) and the kernel-row weight gradient for the consumer."""
-        if not (self.fuse_bn_fwd and kind == "dense" and self.halo_addressable(B, l.S)):
+        c = l.next
+        if not (self.fuse_bn_fwd and kind == "dense" and self.halo_addressable(B, l.S)) or c is None:
             return False
-        if l.cin == 1 and os.environ.get("CDM_FUSE_CIN1_FWD", "1") == "0":   # A/B switch of the init conv's fusion
-            return False
-        i = self.layers.index(l)
-        if i + 1 >= len(self.layers):
-            return False
-        c = self.layers[i + 1]
         widths = (32, 64, 128, 256) if self.h3 else (32, 64)     # the wide-row LDS-halo conv is h3-only
         halo = lambda L: L.kc == 16 and L.S in widths and (L.S * L.S) % 256 == 0   # noqa: E731
         # the producer's max / min of y: from its conv epilogue (LDS-halo path), or from the statistics pass of the
@@ -418,48 +441,31 @@ class UNetEngine:
         return ((l.cin == 1 or halo(l)) and halo(c) and c.cin == l.cout and c.cin <= 256 and c.cin % 128 == 0
                 and c.cout % 128 == 0 and c.S == l.S)
 
-    def fuses_gn_out(self, train: bool) -> bool:
+    def fuses_gn_out(self) -> bool:
         """out.1's GroupNorm + ReLU runs inside out.3's kernels (forward; train: and its weight gradient): zO is never
         written, and its workspace buffer is not allocated."""
         nf, H = self.nf, self.H
-        return (self.cp == 1 and (not train or self.fuse_gn_out) and nf % 16 == 0 and H <= 256 and 256 % H == 0)
+        return self.cp == 1 and nf % 16 == 0 and H <= 256 and 256 % H == 0
 
     def fuses_bn_bwd(self, l: "LayerSpec", kind: str, B: int = 1) -> bool:
-        """Layer l's BN backward runs inside its dgrad / wgrad staging (cdm_conv3x3_*_h3_bnbwd)."""
-        return (self.fuse_bn_bwd and kind in ("dense", "plain", "resid") and l.cin > 1 and l is not self.layers[0]
+        """Layer l's BN backward runs inside its dgrad staging (cdm_conv3x3_dgrad_x16_bnbwd_dy), which hands dy to its
+        weight gradient."""
+        return (self.fuse_bn_bwd and kind in ("dense", "plain", "resid") and l.cin > 1 and l.index > 0
                 and l.S in ((32, 64, 128) if self.h3 else (32, 64))
                 and self.halo_addressable(B, l.S)
                 and l.kc == 16 and l.cin % 128 == 0 and l.cout % 128 == 0 and l.cout <= 256)
 
     # h3 operand maxima: one device slot per producer, zeroed at the start of every forward --------------
     def _slot(self, ws, key):
-        """Pointer to the amax slot `key` of this workspace (None unless the arithmetic is h3)."""
-        if self.nterm != NT_H3:
+        """Pointer to the amax slot `key` of this workspace, assigned on first use (None unless the arithmetic is h3;
+        None for no key — the image of in_channels > 1 has none: its max is measured by the conv call)."""
+        if self.nterm != NT_H3 or key is None:
             return None
         i = ws.aslot.get(key)
         if i is None:
             i = ws.aslot[key] = len(ws.aslot)
             assert i < ws.amax.numel()
         return _p(ws.amax) + 4 * i
-
-    # producers writing slices of one concatenation buffer share that buffer's slot (its consumers read the
-    # whole buffer, or a slice whose max the shared slot bounds from above — harmless for the scale)
-    _CAT_SLOT = {"init_conv.conv2": "catO", "up2.model.2.conv2": "catO", "down1.model.1.conv2": "catU2",
-                 "up1.model.2.conv2": "catU2", "down2.model.1.conv2": "catU1"}
-
-    def _dst_slot(self, ws, l: "LayerSpec"):
-        return self._slot(ws, self._CAT_SLOT.get(l.name, "z:" + l.name))
-
-    def _src_slot(self, ws, l: "LayerSpec"):
-        special = {"down1.model.0.conv1": "catO", "down2.model.0.conv1": "catU2",
-                   "up1.model.1.conv1": "yT1", "up2.model.1.conv1": "yT2"}
-        if l.name in special:
-            return self._slot(ws, special[l.name])
-        i = self.layers.index(l)
-        if i == 0:
-            return None            # the image (in_channels > 1): its max is measured by the conv call
-        prev = self.layers[i - 1]
-        return self._dst_slot(ws, prev)
 
     # ------------------------------------------------------------------------------------------
     def workspace(self, B: int, train: bool, frozen: bool = False) -> "Workspace":
@@ -483,7 +489,7 @@ class UNetEngine:
         Returns eps [B, H, W] (in_channels > 1: NHWC [B*H*W, cp]; written into ``out`` when given)."""
         lb = lib(); s = stream
         nf, H, B = self.nf, self.H, ws.B
-        H1, H2 = H // 2, H // 4
+        H2 = H // 4
         train = ws.train
         assert train or not frozen
         assert not (frozen and ws.act16), "eval-mode forwards keep fp32 activations: use workspace(B, True, frozen=True)"
@@ -492,7 +498,7 @@ class UNetEngine:
         ws.x_in = x
         if self.cp > 1:
             assert x.numel() == B * H * H * self.cp
-            ws.src["init_conv.conv1"] = Act(x, self.cp)
+            ws.plan[0].src = Act(x, self.cp)
         ws.sc_pending = (sc_w, sc_b, sc_split)
         if self.nterm == NT_H3:
             lb.cdm_zero_f32(_p(ws.amax), ws.amax.numel(), s)
@@ -502,10 +508,8 @@ class UNetEngine:
             lb.cdm_fill_i32(_p(ws.ymm) + 4 * half, half, 2 ** 31 - 1, s)  # min keys
         # ---------------- encoder ----------------
         probe = self.stage_probe or (lambda stage, ws_: None)
-        for i, l in enumerate(self.layers[:10]):
-            self._conv_bn_fwd(ws, P, l, s, x)
-            if i in (1, 5, 9):
-                probe({1: "x0", 5: "d1", 9: "d2"}[i], ws)
+        for stage in ("init", "down1", "down2"):
+            self._stage_fwd(ws, P, stage, s, x)
         # ---------------- to_vec ----------------
         d2 = ws.catU1.sl(2 * nf, 2 * nf)
         lb.cdm_reduce_sum(d2.p, d2.ld, B, H2 * H2, 2 * nf, H2 * H2, _p(ws.hsum), s)
@@ -553,30 +557,22 @@ class UNetEngine:
         lb.cdm_norm_apply_fwd(APPLY_FILM | APPLY_RELU, _p(ws.y0), c0, B, H2, H2, c0, _p(ws.gn0["scale"]),
                               _p(ws.gn0["shift"]), c0, _p(ce1), c0 if rows_c > 1 else 0, _p(te1),
                               c0 if rows_t > 1 else 0, None, None, None, 0, u1.p, u1.ld, self._slot(ws, "catU1"), s)
-        # ---------------- up1 ----------------
-        self.convT2x2(ws, "up1.model.0", ws.catU1, B, H2, 4 * nf, P, ws.yT1, "catU1", "yT1", s)
-        for l in self.layers[10:14]:
-            self._conv_bn_fwd(ws, P, l, s, x)
-        probe("film2", ws)
-        # ---------------- up2 ----------------
-        self.convT2x2(ws, "up2.model.0", ws.catU2, B, H1, 2 * nf, P, ws.yT2, "catU2", "yT2", s)
-        for l in self.layers[14:18]:
-            self._conv_bn_fwd(ws, P, l, s, x)
-        probe("u3", ws)
+        # ---------------- up1, up2 ----------------
+        for ct in self.convT:
+            self.convT2x2(ws, ct, P, s)
+            self._stage_fwd(ws, P, ct.stage, s, x)
         # ---------------- out ----------------
         self.conv3x3("out.0.wpk", ws.catO.p, B, H, 2 * nf, 2 * nf, _p(P["out.0.bias"]), _p(ws.yO), nf, nf, 0,
                      _p(ws.slab), nf, self.kc_out0, s, amax_x=self._slot(ws, "catO"))
         probe("yO", ws)
         # out.1's GroupNorm statistics come from out.0's epilogue partials (128-pixel tiles) when no tile spans two images
         self._gn_fwd(ws, P, "out.1", Act(ws.yO, nf), B, H, nf, ws.gnO, stats_from_conv=(H * H) % CHUNK == 0, stream=s)
-        if self.fuses_gn_out(train):
+        if self.fuses_gn_out():
             # out.1's GroupNorm + ReLU applied in out.3's staging (train: and in out.3's weight gradient): zO never
             # written
             lb.cdm_conv3x3_cout1_fwd_gn(_p(ws.yO), nf, B, H, H, nf, _p(ws.gnO["scale"]), _p(ws.gnO["shift"]),
                                         _p(P["out.3.weight"]), _p(P["out.3.bias"]), _p(eps), s)
-            ws.zO_fused = train
             return eps
-        ws.zO_fused = False
         zslot = self._slot(ws, "zO") if self.cp > 1 else None
         lb.cdm_norm_apply_fwd(APPLY_RELU, _p(ws.yO), nf, B, H, H, nf, _p(ws.gnO["scale"]), _p(ws.gnO["shift"]), nf,
                               None, 0, None, 0, None, None, None, 0, _p(ws.zO), nf, zslot, s)
@@ -587,136 +583,124 @@ class UNetEngine:
         lb.cdm_conv3x3_cout1_fwd(_p(ws.zO), nf, B, H, H, nf, _p(P["out.3.weight"]), _p(P["out.3.bias"]), _p(eps), s)
         return eps
 
-    def convT2x2(self, ws, name, x: Act, B, Hin, cin, P, y, src_slot, dst_slot, s):
+    def _stage_fwd(self, ws, P, stage, s, x):
+        for l in self.stages[stage]:
+            (self._conv_bn_train if ws.train else self._conv_bn_eval)(ws, ws.plan[l.index], P, s, x)
+        if self.stage_probe is not None:
+            self.stage_probe(STAGE_PROBE[stage], ws)
+
+    def convT2x2(self, ws, ct: ConvTSpec, P, s):
         """ConvTranspose2d(cin, nf, 2, 2) (diffusion_utilities.py:86) of x [B,Hin,Hin,cin] into y [B,2Hin,2Hin,nf]."""
-        nf = self.nf
+        nf, B, Hin, cin, name = self.nf, ws.B, ct.Hin, ct.cin, ct.name
+        x, y = getattr(ws, ct.src), getattr(ws, ct.dst)
         if self.x16:
             lib().cdm_convT2x2_fwd_x16(x.p, B, Hin, Hin, cin, x.ld, _p(self.pk[name + ".wt_x"]),
-                                       self._slot(ws, src_slot), self._wamax(name + ".wt"), _p(P[name + ".bias"]),
-                                       _p(y), nf, nf, self._slot(ws, dst_slot), self.nterm, s)
+                                       self._slot(ws, ct.src), self._wamax(name + ".wt"), _p(P[name + ".bias"]),
+                                       _p(y), nf, nf, self._slot(ws, ct.dst), self.nterm, s)
         else:
             lib().cdm_convT2x2_fwd(x.p, B, Hin, Hin, cin, x.ld, _p(self.pk[name + ".wt"]), _p(P[name + ".bias"]),
-                                   _p(y), nf, nf, self._slot(ws, dst_slot), s)
+                                   _p(y), nf, nf, self._slot(ws, ct.dst), s)
 
-    def _conv_bn_fwd(self, ws, P, l: LayerSpec, s, x):
+    def _conv_bn_train(self, ws, p: "LayerPlan", P, s, x):
+        """Train forward of one layer: the conv with the statistics partials in its epilogue, the BatchNorm finalize,
+        and the apply — unless the next conv's staging applies z = relu(y s + t) itself (p.fused_fwd)."""
         lb = lib()
+        l, y, st = p.l, p.y, p.bn
         B, S = ws.B, l.S
-        src = ws.src[l.name]
-        y = ws.y[l.name]
-        st = ws.bn[l.name]
-        npix = B * S * S
-        if ws.train:
-            if l.cin == 1:
-                lb.cdm_conv3x3_cin1_fwd(_p(x), B, S, S, _p(self.pk[l.name + ".wpk"]), _p(P[l.b]), _p(y), l.cout,
-                                        l.cout, 0, None, s)
-                ymm_p, ymm_ld = ws.ymm_of(l) if (l.name in ws.fused_fwd and self.h3) else (None, 0)
-                lb.cdm_reduce_stats_mm(_p(y), l.cout, B, S * S, l.cout, CHUNK, _p(ws.slab), ymm_p, ymm_ld, s)
-                ntiles = B * _cdiv(S * S, CHUNK)
-            else:
-                yslot = self._slot(ws, "y:" + l.name) if l.name in ws.fused else None
-                src, pre = self._src_pre(ws, l)
-                ymm = ws.ymm_of(l) if (l.name in ws.fused_fwd and self.h3) else None
-                self.conv3x3(l.name + ".wpk", src.p, B, S, l.cin, src.ld, _p(P[l.b]), _p(y), l.cout, l.cout, 0,
-                             _p(ws.slab), l.cout, l.kc, s, amax_x=self._src_slot(ws, l), amax_y=yslot, pre=pre,
-                             ymm=ymm, dt=self._fwd_dt(ws, l, pre))
-                ntiles = _cdiv(npix, CHUNK)
-            bn = l.bn
-            nparts = fold(ws, _p(ws.slab), ntiles, 2, l.cout, s)
-            fused_fwd = l.name in ws.fused_fwd
-            ymm_p, ymm_ld = ws.ymm_of(l) if (fused_fwd and self.h3) else (None, 0)
-            if ws.frozen:
-                lb.cdm_bn_fwd_frozen(l.cout, _p(P[bn + ".weight"]), _p(P[bn + ".bias"]), _p(P[bn + ".running_mean"]),
-                                     _p(P[bn + ".running_var"]), BN_EPS, _p(st["mean"]), _p(st["invstd"]),
-                                     _p(st["scale"]), _p(st["shift"]), ymm_p, ymm_ld,
-                                     self._dst_slot(ws, l) if fused_fwd else None, s)
-            else:
-                lb.cdm_bn_fwd_finalize(_p(ws.dpart), nparts, 2, l.cout, float(npix), _p(P[bn + ".weight"]),
-                                       _p(P[bn + ".bias"]), _p(P[bn + ".running_mean"]), _p(P[bn + ".running_var"]),
-                                       _p(P[bn + ".num_batches_tracked"]), BN_MOM, BN_EPS, _p(st["mean"]),
-                                       _p(st["invstd"]), _p(st["scale"]), _p(st["shift"]), ymm_p, ymm_ld,
-                                       self._dst_slot(ws, l) if fused_fwd else None, s)
-            if fused_fwd:
-                return                    # z = relu(y s + t) is applied by the next conv's staging
-            scale, shift, relu = st["scale"], st["shift"], APPLY_RELU
+        ymm_p, ymm_ld = p.ymm or (None, 0)
+        if l.cin == 1:
+            lb.cdm_conv3x3_cin1_fwd(_p(x), B, S, S, _p(self.pk[l.name + ".wpk"]), _p(P[l.b]), _p(y), l.cout,
+                                    l.cout, 0, None, s)
+            lb.cdm_reduce_stats_mm(_p(y), l.cout, B, S * S, l.cout, CHUNK, _p(ws.slab), ymm_p, ymm_ld, s)
+            ntiles = B * _cdiv(S * S, CHUNK)
         else:
-            kind = ws.dst_kind[l.name]
-            dense = kind in ("dense", "plain")
-            outp = ws.dst[l.name] if dense else Act(y, l.cout)
-            dslot = self._dst_slot(ws, l) if dense else None
-            if l.cin == 1:
-                lb.cdm_conv3x3_cin1_fwd(_p(x), B, S, S, _p(self.pk[l.name + ".wpk_e"]),
-                                        _p(self.pk[l.name + ".bpk_e"]), outp.p, outp.ld, l.cout, 1, dslot, s)
-            elif not dense and self.fuses_eval(l, B):
-                # the residual add / FiLM / MaxPool in the conv's epilogue: y is never written
-                self._conv_eval_fused(ws, l, kind, x, s)
-                return
-            else:
-                self.conv3x3(l.name + ".wpk_e", src.p, B, S, l.cin, src.ld, _p(self.pk[l.name + ".bpk_e"]), outp.p,
-                             outp.ld, l.cout, EPI_RELU, None, 0, l.kc, s, amax_x=self._src_slot(ws, l),
-                             amax_y=dslot)
-            if dense:
-                return
-            scale, shift, relu = self._ones, self._zeros, 0
-        # apply: z = relu(bn(y)) -> destination (dense / pool / film / resid)
-        kind = ws.dst_kind[l.name]
-        dst = ws.dst[l.name]
-        C = l.cout
-        am = self._dst_slot(ws, l)
-        if kind == "dense" or kind == "plain":
-            lb.cdm_norm_apply_fwd(relu, _p(y), C, B, S, S, C, _p(scale), _p(shift), 0, None, 0, None, 0, None, None,
-                                  None, 0, dst.p, dst.ld, am, s)
-        elif kind == "pool":
-            lb.cdm_norm_apply_fwd(APPLY_POOL | relu, _p(y), C, B, S, S, C, _p(scale), _p(shift), 0, None, 0, None, 0,
-                                  None, None, None, 0, dst.p, dst.ld, am, s)
-        elif kind == "film":
-            ce, te = ws.emb["contextembed2"], ws.emb["timeembed2"]
-            lb.cdm_norm_apply_fwd(APPLY_FILM | relu, _p(y), C, B, S, S, C, _p(scale), _p(shift), 0, _p(ce),
-                                  C if ws.c_rows > 1 else 0, _p(te), C if ws.t_rows > 1 else 0, None, None, None, 0,
-                                  dst.p, dst.ld, am, s)
-        elif kind == "resid" and self.cp > 1:
-            sc_w, sc_b, split = ws.sc_pending
-            lb.cdm_norm_apply_fwd_resid_c(relu, _p(y), C, B, S, S, C, _p(scale), _p(shift), _p(x), self.cp, self.cimg,
-                                          _p(sc_w), _p(sc_b), split, dst.p, dst.ld, am, s)
-        elif kind == "resid":
-            sc_w, sc_b, split = ws.sc_pending
-            lb.cdm_norm_apply_fwd(APPLY_RESID | relu, _p(y), C, B, S, S, C, _p(scale), _p(shift), 0, None, 0, None,
-                                  0, _p(x), _p(sc_w), _p(sc_b), split, dst.p, dst.ld, am, s)
+            yslot = self._slot(ws, "y:" + l.name) if p.fused else None
+            self.conv3x3(l.name + ".wpk", p.src.p, B, S, l.cin, p.src.ld, _p(P[l.b]), _p(y), l.cout, l.cout, 0,
+                         _p(ws.slab), l.cout, l.kc, s, amax_x=self._slot(ws, l.src_slot), amax_y=yslot, pre=p.pre,
+                         ymm=p.ymm, dt=p.dt_fwd)
+            ntiles = _cdiv(B * S * S, CHUNK)
+        bn = l.bn
+        nparts = fold(ws, _p(ws.slab), ntiles, 2, l.cout, s)
+        zslot = self._slot(ws, l.dst_slot) if p.fused_fwd else None
+        if ws.frozen:
+            lb.cdm_bn_fwd_frozen(l.cout, _p(P[bn + ".weight"]), _p(P[bn + ".bias"]), _p(P[bn + ".running_mean"]),
+                                 _p(P[bn + ".running_var"]), BN_EPS, _p(st["mean"]), _p(st["invstd"]),
+                                 _p(st["scale"]), _p(st["shift"]), ymm_p, ymm_ld, zslot, s)
         else:
-            raise AssertionError(kind)
+            lb.cdm_bn_fwd_finalize(_p(ws.dpart), nparts, 2, l.cout, float(B * S * S), _p(P[bn + ".weight"]),
+                                   _p(P[bn + ".bias"]), _p(P[bn + ".running_mean"]), _p(P[bn + ".running_var"]),
+                                   _p(P[bn + ".num_batches_tracked"]), BN_MOM, BN_EPS, _p(st["mean"]),
+                                   _p(st["invstd"]), _p(st["scale"]), _p(st["shift"]), ymm_p, ymm_ld, zslot, s)
+        if not p.fused_fwd:
+            self._apply(ws, p, st["scale"], st["shift"], APPLY_RELU, x, s)
+
+    def _conv_bn_eval(self, ws, p: "LayerPlan", P, s, x):
+        """Eval forward of one layer: BatchNorm folded into the packed weights, ReLU in the conv's epilogue; a pool /
+        FiLM / residual output transform in that epilogue too (fuses_eval), else by the apply kernel from y."""
+        l = p.l
+        B, S = ws.B, l.S
+        dense = l.kind in ("dense", "plain")
+        outp = p.dst if dense else Act(p.y, l.cout)
+        dslot = self._slot(ws, l.dst_slot) if dense else None
+        if l.cin == 1:
+            lib().cdm_conv3x3_cin1_fwd(_p(x), B, S, S, _p(self.pk[l.name + ".wpk_e"]), _p(self.pk[l.name + ".bpk_e"]),
+                                       outp.p, outp.ld, l.cout, 1, dslot, s)
+        elif not dense and self.fuses_eval(l, B):
+            self._conv_eval_fused(ws, p, x, s)       # y is never written
+            return
+        else:
+            self.conv3x3(l.name + ".wpk_e", p.src.p, B, S, l.cin, p.src.ld, _p(self.pk[l.name + ".bpk_e"]), outp.p,
+                         outp.ld, l.cout, EPI_RELU, None, 0, l.kc, s, amax_x=self._slot(ws, l.src_slot), amax_y=dslot)
+        if not dense:
+            self._apply(ws, p, self._ones, self._zeros, 0, x, s)
+
+    def _transform_operands(self, ws, l: LayerSpec, x):
+        """(sc_x, sc_w, sc_b, split), (film_a, film_a_ld, film_b, film_b_ld) of layer l's output transform: the image
+        and the shortcut draws of a "resid" layer, the second embeddings of the "film" layer, null for the others."""
+        if l.kind == "resid":
+            sc_w, sc_b, split = ws.sc_pending
+            return (_p(x), _p(sc_w), _p(sc_b), split), (None, 0, None, 0)
+        if l.kind == "film":
+            C = l.cout
+            return (None, None, None, 0), (_p(ws.emb["contextembed2"]), C if ws.c_rows > 1 else 0,
+                                           _p(ws.emb["timeembed2"]), C if ws.t_rows > 1 else 0)
+        return (None, None, None, 0), (None, 0, None, 0)
+
+    def _apply(self, ws, p: "LayerPlan", scale, shift, relu, x, s):
+        """z = [relu](y scale + shift), through the layer's output transform, into its destination."""
+        l, dst = p.l, p.dst
+        B, S, C = ws.B, l.S, l.cout
+        am = self._slot(ws, l.dst_slot)
+        if l.kind == "resid" and self.cp > 1:
+            sc_w, sc_b, split = ws.sc_pending
+            lib().cdm_norm_apply_fwd_resid_c(relu, _p(p.y), C, B, S, S, C, _p(scale), _p(shift), _p(x), self.cp,
+                                             self.cimg, _p(sc_w), _p(sc_b), split, dst.p, dst.ld, am, s)
+            return
+        resid, film = self._transform_operands(ws, l, x)
+        flags = {"pool": APPLY_POOL, "film": APPLY_FILM, "resid": APPLY_RESID}.get(l.kind, 0) | relu
+        lib().cdm_norm_apply_fwd(flags, _p(p.y), C, B, S, S, C, _p(scale), _p(shift), 0, *film, *resid, dst.p, dst.ld,
+                                 am, s)
 
     def fuses_eval(self, l: "LayerSpec", B: int) -> bool:
         """Eval forward of a pool / FiLM / residual layer with its output transform in the LDS-halo conv's epilogue
         (cdm_conv3x3_fwd_x16_fused: 32^2 / 64^2 maps, 16-bit arithmetics); $CDM_FUSE_EVAL=0 keeps the apply kernel."""
         return (self.fuse_eval and l.cin > 1 and l.kc == 16 and l.S in (32, 64) and l.cout % 128 == 0
-                and self.halo_addressable(B, l.S) and not (self.cp > 1 and l.name == "init_conv.conv2"))
+                and self.halo_addressable(B, l.S) and not (self.cp > 1 and l.kind == "resid"))
 
-    def _conv_eval_fused(self, ws, l: "LayerSpec", kind: str, x, s):
+    def _conv_eval_fused(self, ws, p: "LayerPlan", x, s):
         lb = lib()
-        B, S, C = ws.B, l.S, l.cout
-        src = ws.src[l.name]
-        dst = ws.dst[l.name]
+        l, src, dst = p.l, p.src, p.dst
+        B, S = ws.B, l.S
         key = l.name + ".wpk_e"
-        amax_x = self._src_slot(ws, l)
+        amax_x = self._slot(ws, l.src_slot)
         if self.h3 and amax_x is None:
             amax_x = _p(self._amax)
             lb.cdm_amax_f32(src.p, B * S * S, l.cin, src.ld, amax_x, 0, s)
-        sc_x = sc_w = sc_b = fa = fb = None
-        split = fan = fbn = 0
-        if kind == "resid":
-            code = 1
-            sc_w_t, sc_b_t, split = ws.sc_pending
-            sc_x, sc_w, sc_b = _p(x), _p(sc_w_t), _p(sc_b_t)
-        elif kind == "film":
-            code = 2
-            fa, fb = _p(ws.emb["contextembed2"]), _p(ws.emb["timeembed2"])
-            fan, fbn = (C if ws.c_rows > 1 else 0), (C if ws.t_rows > 1 else 0)
-        else:
-            assert kind == "pool", kind
-            code = 3
+        resid, film = self._transform_operands(ws, l, x)
         lb.cdm_conv3x3_fwd_x16_fused(src.p, B, S, S, l.cin, src.ld, _p(self.pk[key + "_x"]), amax_x,
-                                     self._wamax(key), _p(self.pk[l.name + ".bpk_e"]), dst.p, dst.ld, C, l.kc,
-                                     self._dst_slot(ws, l), code, sc_x, sc_w, sc_b, split, fa, fan, fb, fbn,
-                                     self.nterm, s)
+                                     self._wamax(key), _p(self.pk[l.name + ".bpk_e"]), dst.p, dst.ld, l.cout, l.kc,
+                                     self._slot(ws, l.dst_slot), {"resid": 1, "film": 2, "pool": 3}[l.kind],
+                                     *resid, *film, self.nterm, s)
 
     def _gn_fwd(self, ws, P, name, y: Act, B, S, C, st, stats_from_conv, stream):
         lb = lib()
@@ -747,14 +731,13 @@ class UNetEngine:
         assert ws.train, "backward needs a train-mode workspace"
         lb = lib(); s = stream
         nf, H, B = self.nf, self.H, ws.B
-        H1, H2 = H // 2, H // 4
-        P0, P1, P2 = B * H * H, B * H1 * H1, B * H2 * H2
+        H2 = H // 4
         # ---------------- out.3 (nf -> 1) ----------------
         if self.cp > 1:
             gO = self._out3_bwd_c(ws, deps, G, s)
         else:
             R = cout1_band_rows(B, H)
-            if ws.zO_fused:
+            if self.fuses_gn_out():
                 lb.cdm_conv3x3_cout1_wgrad_gn(_p(deps), _p(ws.yO), nf, B, H, H, nf, _p(ws.gnO["scale"]),
                                               _p(ws.gnO["shift"]), -R, _p(ws.slab), s)
             else:
@@ -774,18 +757,13 @@ class UNetEngine:
         self._wgrad3x3(ws, Act(dyO, nf), ws.catO, B, H, 2 * nf, nf, G["out.0.weight"], s, amax_dy=dslot,
                        amax_x=self._slot(ws, "catO"))
         self.conv3x3("out.0.wdg", _p(dyO), B, H, nf, nf, None, ws.dcatO.p, ws.dcatO.ld, 2 * nf, 0, None, 0,
-                     self.kc_out0, s, amax_x=dslot,
-                     amax_y=self._slot(ws, ws.out0_g_key) if ws.out0_g_key else None)
+                     self.kc_out0, s, amax_x=dslot, amax_y=self._slot(ws, ws.out0_g_key))
         hook("out")
-        # ---------------- up2 blocks ----------------
-        self._chain_bwd(ws, P, self.layers[14:18], G, s)
-        # convT2 (2nf@H1 -> nf@H): grad wrt its output sits in ws.gT2
-        self._convT_bwd(ws, P, "up2.model.0", Act(ws.gT2, nf), ws.catU2, B, H1, 2 * nf, nf, ws.dcatU2, G, s)
-        hook("up2")
-        # ---------------- up1 blocks (last one carries FiLM2) ----------------
-        self._chain_bwd(ws, P, self.layers[10:14], G, s)
-        self._convT_bwd(ws, P, "up1.model.0", Act(ws.gT1, nf), ws.catU1, B, H2, 4 * nf, nf, ws.dcatU1, G, s)
-        hook("up1")
+        # ---------------- up2, up1 (its last conv carries FiLM2): the blocks, then the ConvT feeding them ----------
+        for ct in reversed(self.convT):
+            self._stage_bwd(ws, P, ct.stage, G, s)
+            self._convT_bwd(ws, P, ct, G, s)
+            hook(ct.stage)
         # ---------------- up0: GroupNorm + ReLU + FiLM1 ----------------
         c0 = 2 * nf
         rows_c, rows_t = ws.c_rows, ws.t_rows
@@ -850,11 +828,10 @@ class UNetEngine:
                                         _p(ws.emb_dpre[mb]), _p(P[mb + ".model.0.weight"]), nf, rows, in_dim, _p(dv), s)
         hook("up0emb")
         # ---------------- down2, down1, init ----------------
-        self._chain_bwd(ws, P, self.layers[6:10], G, s)
-        hook("down2")
-        self._chain_bwd(ws, P, self.layers[2:6], G, s)
-        hook("down1")
-        self._chain_bwd(ws, P, self.layers[0:2], G, s)
+        for stage in ("down2", "down1"):
+            self._stage_bwd(ws, P, stage, G, s)
+            hook(stage)
+        self._stage_bwd(ws, P, "init", G, s)
         if dx is not None:
             if self.cp > 1:
                 self._image_grad_c(ws, dx, s)
@@ -882,18 +859,17 @@ class UNetEngine:
 
     def _image_grad_c(self, ws, dx: torch.Tensor, s: int):
         """dL/dx for in_channels > 1 (NHWC [B*H*W, cp]): init_conv.conv1's input gradient (its dgrad, already in
-        ws.dgrad_dst) plus the random 1x1 shortcut's, dx[p][k] += sum_n g_res[p][n] w[n][k] (one GEMM)."""
+        its plan's dgrad_dst) plus the random 1x1 shortcut's, dx[p][k] += sum_n g_res[p][n] w[n][k] (one GEMM)."""
         lb = lib()
         nf, H, B, cp, C = self.nf, self.H, ws.B, self.cp, self.cimg
-        l = self.layers[0]
         P0 = B * H * H
-        gd = ws.dgrad_dst[l.name]
+        gd = ws.plan[0].dgrad_dst
         dx.view(P0, cp).copy_(gd.buf.view(-1)[: P0 * gd.ld].view(P0, gd.ld)[:, :cp])
         sc_w, _, split = ws.sc_pending
         assert split >= B, "input gradients with two shortcut draws (CFG halves) are not a module-call form"
         wpad = self._buf("sc.wpad", (nf, cp))
         wpad[:, C:].zero_(); wpad[:, :C].copy_(sc_w[: nf * C].view(nf, C))
-        gres = ws.gout["init_conv.conv2"]
+        gres = ws.plan[1].gout
         sp = lib().raw("cdm_gemm_splits")(nf, 1)
         lb.cdm_gemm_f32(gres.p, gres.ld, P0, nf, _p(wpad), cp, cp, _p(dx), cp, None, 1, EPI_ACCUM, sp, _p(ws.slab), s)
 
@@ -902,33 +878,24 @@ class UNetEngine:
         init_conv.conv1's input gradient (the tap-flipped 3x3 conv over its BatchNorm + ReLU backward, applied while
         reading g and y) plus the random 1x1 shortcut's (sum_c w[c] * grad of the block output).  Runs after the init
         conv's backward, whose BatchNorm coefficients ws.coef still hold."""
-        l = self.layers[0]
+        p, l = ws.plan[0], self.layers[0]
         C, B, H = l.cout, ws.B, self.H
-        st, co = ws.bn[l.name], ws.coef
-        g = ws.gout[l.name]
-        gres = ws.gout["init_conv.conv2"]
+        st, co = p.bn, ws.coef
+        g, gres = p.gout, ws.plan[1].gout
         sc_w, _, split = ws.sc_pending
-        if self.fuse_cin1_bwd:
-            lib().cdm_conv3x3_cin1_dgrad(g.p, g.ld, _p(ws.y[l.name]), C, _p(st["scale"]), _p(st["shift"]),
-                                         _p(st["mean"]), _p(st["invstd"]), _p(co[0]), _p(co[1]), _p(co[2]),
-                                         _p(P[l.w]), gres.p, gres.ld, _p(sc_w), split, B, H, H, C, _p(dx), s)
-        else:                                   # dy1 was written by cdm_norm_apply_bwd
-            dy = ws.dy[l.name]
-            lib().cdm_conv3x3_cin1_dgrad(dy.p, dy.ld, None, 0, None, None, None, None, None, None, None, _p(P[l.w]),
-                                         gres.p, gres.ld, _p(sc_w), split, B, H, H, C, _p(dx), s)
+        lib().cdm_conv3x3_cin1_dgrad(g.p, g.ld, _p(p.y), C, _p(st["scale"]), _p(st["shift"]), _p(st["mean"]),
+                                     _p(st["invstd"]), _p(co[0]), _p(co[1]), _p(co[2]), _p(P[l.w]), gres.p, gres.ld,
+                                     _p(sc_w), split, B, H, H, C, _p(dx), s)
 
-    def _chain_bwd(self, ws, P, layers, G, s):
-        for l in reversed(layers):
-            self._conv_bn_bwd(ws, P, l, G, s)
+    def _stage_bwd(self, ws, P, stage, G, s):
+        for l in reversed(self.stages[stage]):
+            self._conv_bn_bwd(ws, ws.plan[l.index], P, G, s)
 
-    def _conv_bn_bwd(self, ws, P, l: LayerSpec, G, s):
+    def _conv_bn_bwd(self, ws, p: "LayerPlan", P, G, s):
         lb = lib()
+        l, g, y, st = p.l, p.gout, p.y, p.bn
         B, S, C = ws.B, l.S, l.cout
-        kind = ws.dst_kind[l.name]
-        g = ws.gout[l.name]
-        y = ws.y[l.name]
-        st = ws.bn[l.name]
-        mode = {"dense": 0, "plain": 0, "resid": 0, "pool": 1, "film": 2}[kind]
+        mode = {"pool": 1, "film": 2}.get(l.kind, 0)
         film_a, film_an = None, 0
         if mode == 2:
             film_a, film_an = ws.emb["contextembed2"], (C if ws.c_rows > 1 else 0)
@@ -936,12 +903,12 @@ class UNetEngine:
         nch = _cdiv(HWp, CHUNK)
         co = ws.coef
         bn = l.bn
-        if l.name in ws.sums_by:
-            # the sums came with the consumer's weight gradient (PreBnReluSums): one partial per split
+        if p.sums_by:
+            # the sums came with the consumer's weight gradient (PreBnReluSums): one partial per block
             assert mode == 0
-            nparts = fold(ws, _p(ws.sums), ws.sums_sp[l.name], 5, C, s)
+            nparts = fold(ws, _p(ws.sums), p.sums_parts, 5, C, s)
         else:
-            assert l.name not in ws.act16, "bf16 activations need the fused BN-backward sums"
+            assert not p.own16, "bf16 activations need the fused BN-backward sums"
             lb.cdm_norm_bwd_reduce(mode, g.p, g.ld, _p(y), C, B, S, S, C, _p(st["scale"]), _p(st["shift"]), 0,
                                    _p(st["mean"]), _p(st["invstd"]), 0, 1, _p(film_a), film_an, CHUNK, _p(ws.slab), s)
             if mode == 2:  # FiLM2 sums -> d cemb2 / d temb2 (per sample)
@@ -951,154 +918,70 @@ class UNetEngine:
         fin = lb.cdm_bn_bwd_finalize_frozen if ws.frozen else lb.cdm_bn_bwd_finalize
         fin(_p(ws.dpart), nparts, C, float(B * S * S), _p(P[bn + ".weight"]), _p(st["invstd"]), _p(G[bn + ".weight"]),
             _p(G[bn + ".bias"]), _p(co[0]), _p(co[1]), _p(co[2]), _p(G[l.b]), s)
-        gslot = self._dgrad_amax_slot(ws, l)
-        if l.name in ws.fused:
-            # dy = bn_bwd(g, y) inside the staging of both convs; its scale from a bound on max|dy|
-            dslot = self._slot(ws, "dy:" + l.name)
+        coef = (_p(st["scale"]), _p(st["shift"]), _p(st["mean"]), _p(st["invstd"]), _p(co[0]), _p(co[1]), _p(co[2]))
+        if l.cin == 1:
+            # init_conv.conv1: only a weight gradient (the input needs none); its BN backward runs while that kernel
+            # reads g and y (dy is never written)
+            lb.cdm_conv3x3_cin1_wgrad_bnbwd(g.p, g.ld, _p(y), C, *coef, _p(ws.x_in), B, S, S, C, CHUNK, _p(ws.slab), s)
+            nparts = fold(ws, _p(ws.slab), B * _cdiv(S * S, CHUNK), 10, C, s)
+            lb.cdm_slab_sum_all(_p(ws.dpart), nparts, 10, 0, 9, C, _p(G[l.w]), 1, 9, 0, s)
+            return
+        # the dgrad goes first: it writes the producer's g, which the weight gradient's producer sums read
+        gslot = self._slot(ws, p.g_slot)
+        dslot = self._slot(ws, "dy:" + l.name)
+        dgd, key = p.dgrad_dst, l.name + ".wdg"
+        accum = EPI_ACCUM if p.dgrad_accum else 0
+        if p.fused:
+            # dy = bn_bwd(g, y) goes from the dgrad to the weight gradient through ws.dyo (g's row stride and element
+            # type), never through a per-layer buffer; its h3 scale comes from a bound on max|dy|
             if self.h3:
                 lb.cdm_bn_bwd_amax_bound(C, _p(co[0]), _p(co[1]), _p(co[2]), _p(st["mean"]), _p(st["invstd"]),
                                          self._slot(ws, "g:" + l.name), self._slot(ws, "y:" + l.name), dslot, s)
-            coef = (_p(st["scale"]), _p(st["shift"]), _p(st["mean"]), _p(st["invstd"]), _p(co[0]), _p(co[1]),
-                    _p(co[2]))
-            src, pre = self._src_pre(ws, l)
-            sp = wgrad_splits(B * S * S, C, 9 * l.cin)
-            # dgrad first: it writes the producer's g, which the weight gradient's producer sums read
-            dgd = ws.dgrad_dst[l.name]
-            key = l.name + ".wdg"
-            own16 = 1 if l.name in ws.act16 else 0
-            if ws.dyo is not None:
-                if self.dy_pass:
-                    # bf16 arithmetic: dy by its own elementwise pass, then the dgrad on the LDS-halo forward schedule
-                    # (halo two chunks ahead, one barrier per chunk) — the fused BN-backward staging has no room for it
-                    lb.cdm_bn_bwd_dy(g.p, g.ld, _p(y), C, B * S * S, C, *coef, _p(ws.dyo), g.ld, own16 | (own16 << 1), s)
-                    self.conv3x3(key, _p(ws.dyo), B, S, C, g.ld, None, dgd.p, dgd.ld, l.cin,
-                                 EPI_ACCUM if ws.dgrad_accum[l.name] else 0, None, 0, l.kc, s, amax_y=gslot,
-                                 dt=own16 | self._dgrad_out16(ws, l))
-                else:
-                    # the dgrad stores dy; the weight gradient stages it (no BN backward there)
-                    lb.cdm_conv3x3_dgrad_x16_bnbwd_dy(g.p, g.ld, _p(y), C, *coef, B, S, S, C, _p(self.pk[key + "_x"]),
-                                                      dslot, self._wamax(key), dgd.p, dgd.ld, l.cin,
-                                                      EPI_ACCUM if ws.dgrad_accum[l.name] else 0, gslot, _p(ws.dyo),
-                                                      self.nterm, own16 | self._dgrad_out16(ws, l), s)
-                nul = (None,) * 7
-                if pre is None:
-                    lb.cdm_conv3x3_wgrad_x16_ex(_p(ws.dyo), g.ld, None, 0, *nul, C, src.p, B, S, S, l.cin, src.ld, None,
-                                                None, None, 0, None, None, None, dslot, self._src_slot(ws, l), sp,
-                                                _p(ws.slab), self.nterm, own16, s)
-                else:
-                    lb.cdm_conv3x3_wgrad_x16_ex(_p(ws.dyo), g.ld, None, 0, *nul, C, src.p, B, S, S, l.cin, src.ld,
-                                                pre[0], pre[1], *self._producer_sums(ws, l, sp), dslot,
-                                                self._src_slot(ws, l), sp, _p(ws.slab), self.nterm,
-                                                own16 | self._prod16(ws, l), s)
-                lb.cdm_slab_reduce(_p(ws.slab), sp, C, 9 * l.cin, _p(G[l.w]), 9 * l.cin, 1, 9, l.cin, 0, 1.0, s)
-                return
-            lb.cdm_conv3x3_dgrad_x16_bnbwd(g.p, g.ld, _p(y), C, *coef, B, S, S, C, _p(self.pk[key + "_x"]), dslot,
-                                           self._wamax(key), dgd.p, dgd.ld, l.cin,
-                                           EPI_ACCUM if ws.dgrad_accum[l.name] else 0, gslot, self.nterm,
-                                           own16 | self._dgrad_out16(ws, l), s)
-            if pre is None:
-                lb.cdm_conv3x3_wgrad_x16_bnbwd(g.p, g.ld, _p(y), C, *coef, C, src.p, B, S, S, l.cin, src.ld, dslot,
-                                               self._src_slot(ws, l), sp, _p(ws.slab), self.nterm, own16, s)
+            if self.nterm == 1:
+                # one-term (bf16) arithmetic: dy by its own elementwise pass, then the dgrad on the LDS-halo forward
+                # schedule (halo two chunks ahead, one barrier per chunk)
+                lb.cdm_bn_bwd_dy(g.p, g.ld, _p(y), C, B * S * S, C, *coef, _p(ws.dyo), g.ld, p.own16 | (p.own16 << 1), s)
+                self.conv3x3(key, _p(ws.dyo), B, S, C, g.ld, None, dgd.p, dgd.ld, l.cin, accum, None, 0, l.kc, s,
+                             amax_y=gslot, dt=p.dt_dgrad)
             else:
-                lb.cdm_conv3x3_wgrad_x16_ex(g.p, g.ld, _p(y), C, *coef, C, src.p, B, S, S, l.cin, src.ld, pre[0],
-                                            pre[1], *self._producer_sums(ws, l, sp), dslot, self._src_slot(ws, l), sp,
-                                            _p(ws.slab), self.nterm, own16 | self._prod16(ws, l), s)
-            lb.cdm_slab_reduce(_p(ws.slab), sp, C, 9 * l.cin, _p(G[l.w]), 9 * l.cin, 1, 9, l.cin, 0, 1.0, s)
+                lb.cdm_conv3x3_dgrad_x16_bnbwd_dy(g.p, g.ld, _p(y), C, *coef, B, S, S, C, _p(self.pk[key + "_x"]),
+                                                  dslot, self._wamax(key), dgd.p, dgd.ld, l.cin, accum, gslot,
+                                                  _p(ws.dyo), self.nterm, p.dt_dgrad, s)
+            self._wgrad_rows(ws, p, _p(ws.dyo), g.ld, dslot, G[l.w], s)
             return
-        if l.cin == 1 and mode == 0 and self.fuse_cin1_bwd:
-            # init_conv.conv1: only a weight gradient (the input needs none); its BN backward runs while that kernel
-            # reads g and y (bit-identical dy, never written)
-            lb.cdm_conv3x3_cin1_wgrad_bnbwd(g.p, g.ld, _p(y), C, _p(st["scale"]), _p(st["shift"]), _p(st["mean"]),
-                                            _p(st["invstd"]), _p(co[0]), _p(co[1]), _p(co[2]), _p(ws.x_in), B, S, S,
-                                            C, CHUNK, _p(ws.slab), s)
-            nparts = fold(ws, _p(ws.slab), B * _cdiv(S * S, CHUNK), 10, C, s)
-            lb.cdm_slab_sum_all(_p(ws.dpart), nparts, 10, 0, 9, C, _p(G[l.w]), 1, 9, 0, s)
-            return
-        dy = ws.dy[l.name]
-        dslot = self._slot(ws, "dy:" + l.name) if l.cin > 1 else None
+        dy = p.dy
         lb.cdm_norm_apply_bwd(mode, g.p, g.ld, _p(y), C, B, S, S, C, _p(st["scale"]), _p(st["shift"]), 0,
                               _p(st["mean"]), _p(st["invstd"]), 0, 1, _p(film_a), film_an, _p(co[0]), _p(co[1]),
                               _p(co[2]), 0, dy.p, dy.ld, dslot, s)
-        src, pre = self._src_pre(ws, l)
-        if l.cin == 1:
-            lb.cdm_conv3x3_cin1_wgrad(dy.p, dy.ld, _p(ws.x_in), B, S, S, C, CHUNK, _p(ws.slab), s)
-            nparts = fold(ws, _p(ws.slab), B * _cdiv(S * S, CHUNK), 10, C, s)
-            lb.cdm_slab_sum_all(_p(ws.dpart), nparts, 10, 0, 9, C, _p(G[l.w]), 1, 9, 0, s)
-            return
-        dgd = ws.dgrad_dst[l.name]
-        # dgrad first (it writes the producer's g, read by the producer sums of the weight gradient below)
-        self.conv3x3(l.name + ".wdg", dy.p, B, S, C, dy.ld, None, dgd.p, dgd.ld, l.cin,
-                     EPI_ACCUM if ws.dgrad_accum[l.name] else 0, None, 0, l.kc, s, amax_x=dslot, amax_y=gslot,
-                     dt=self._dgrad_out16(ws, l))
-        pad0 = l is self.layers[0] and self.cp > self.cimg      # the init conv's zero image-channel columns
+        self.conv3x3(key, dy.p, B, S, C, dy.ld, None, dgd.p, dgd.ld, l.cin, accum, None, 0, l.kc, s, amax_x=dslot,
+                     amax_y=gslot, dt=p.dt_dgrad)
+        pad0 = l.index == 0 and self.cp > self.cimg             # the init conv's zero image-channel columns
         gW = self._buf("init.gwpad", (C, self.cp, 3, 3)) if pad0 else G[l.w]
-        self._wgrad3x3(ws, dy, src, B, S, l.cin, C, gW, s, amax_dy=dslot, amax_x=self._src_slot(ws, l), pre=pre,
-                       sums_of=l)
+        if p.pre is not None:
+            self._wgrad_rows(ws, p, dy.p, dy.ld, dslot, gW, s)
+        else:
+            self._wgrad3x3(ws, dy, p.src, B, S, l.cin, C, gW, s, amax_dy=dslot, amax_x=self._slot(ws, l.src_slot))
         if pad0:
             G[l.w].copy_(gW[:, :self.cimg])
 
-    def _src_pre(self, ws, l: "LayerSpec"):
-        """(input activation, BN-ReLU transform or None) of conv l in train mode: a fused producer hands over its
-        pre-norm output y and its (scale, shift) instead of z."""
-        i = self.layers.index(l)
-        if i > 0 and self.layers[i - 1].name in ws.fused_fwd:
-            p = self.layers[i - 1]
-            st = ws.bn[p.name]
-            return Act(ws.y[p.name], p.cout), (_p(st["scale"]), _p(st["shift"]))
-        return ws.src[l.name], None
+    def _wgrad_rows(self, ws, p: "LayerPlan", dy_p, lddy, amax_dy, gW, s):
+        """Kernel-row weight gradient of p's layer into gW (OIHW) from a stored dy [pix][C_out] (row stride lddy).  X is
+        the plan's source: plain, or relu(x s + t) of a fused producer's y (p.pre), whose BN-backward channel sums then
+        ride along where the plan says so (p.sums_from: the producer's g was written by this layer's dgrad)."""
+        lb = lib()
+        l, x, q = p.l, p.src, p.sums_from
+        B, S, C = ws.B, l.S, l.cout
+        x_s, x_t = p.pre or (None, None)
+        sums = (q.gout.p, q.gout.ld, _p(q.bn["mean"]), _p(q.bn["invstd"]), _p(ws.sums)) if q else (None, 0) + (None,) * 3
+        lb.cdm_conv3x3_wgrad_x16_ex(dy_p, lddy, None, 0, *(None,) * 7, C, x.p, B, S, S, l.cin, x.ld, x_s, x_t, *sums,
+                                    amax_dy, self._slot(ws, l.src_slot), p.sp, _p(ws.slab), self.nterm, p.dt_wgrad, s)
+        # slab[z][co][tap*cin+ci] -> OIHW [co][ci][tap]
+        lb.cdm_slab_reduce(_p(ws.slab), p.sp, C, 9 * l.cin, _p(gW), 9 * l.cin, 1, 9, l.cin, 0, 1.0, s)
 
-    # bf16 activation storage (C4): dtype bits of the conv launches around layer l ---------------------------------
-    def _prod16(self, ws, l: "LayerSpec") -> int:
-        """2 when conv l's input is the bf16 pre-norm output of a fused producer (its staging applies BN-ReLU), else 0."""
-        i = self.layers.index(l)
-        return 2 if (i > 0 and self.layers[i - 1].name in ws.act16 and self.layers[i - 1].name in ws.fused_fwd) else 0
-
-    def _fwd_dt(self, ws, l: "LayerSpec", pre) -> int:
-        """forward conv l: bit 0 its source is a bf16 y (BN-ReLU staged), bit 1 its y is stored as bf16."""
-        src16 = 1 if (pre is not None and self._prod16(ws, l)) else 0
-        return src16 | (2 if l.name in ws.act16 else 0)
-
-    def _dgrad_out16(self, ws, l: "LayerSpec") -> int:
-        """2 when the input gradient conv l writes (the gradient of its producer's output) is stored as bf16."""
-        i = self.layers.index(l)
-        if i == 0 or ws.dgrad_accum.get(l.name, False):
-            return 0
-        p = self.layers[i - 1]
-        return 2 if (p.name in ws.act16 and ws.gout[p.name].buf.data_ptr() == ws.dgrad_dst[l.name].buf.data_ptr()) else 0
-
-    def _dgrad_amax_slot(self, ws, l: "LayerSpec"):
-        """Slot that receives max|dgrad output| of layer l: the grad wrt a ConvT output (h3 ConvT backward) or
-        the grad g of a fused layer (its dy bound)."""
-        if l.name in self._CONVT_GRAD_PRODUCERS:
-            return self._slot(ws, "gT:" + l.name)
-        key = ws.g_amax_key.get(l.name)
-        return self._slot(ws, key) if key else None
-
-    # the dgrads that write the gradient wrt a ConvT output (gT1 / gT2) also record its max for the h3 ConvT bwd
-    _CONVT_GRAD_PRODUCERS = {"up1.model.1.conv1": "up1.model.0", "up2.model.1.conv1": "up2.model.0"}
-
-    def _producer_sums(self, ws, l: "LayerSpec", sp: int):
-        """(x_g, ldxg, x_mean, x_invstd, x_sums) for conv l's weight gradient: the BN-backward sums of its fused producer
-        when they ride along (ws.sums_from), else all null."""
-        pn = ws.sums_from.get(l.name)
-        if pn is None:
-            return None, 0, None, None, None
-        g, st = ws.gout[pn], ws.bn[pn]
-        ws.sums_sp[pn] = sp * 3 * (l.cout // 128)     # one partial per block: split x kernel row x co tile
-        return g.p, g.ld, _p(st["mean"]), _p(st["invstd"]), _p(ws.sums)
-
-    def _wgrad3x3(self, ws, dy: Act, x: Act, B, S, cin, cout, gW, s, amax_dy=None, amax_x=None, pre=None,
-                  sums_of=None):
+    def _wgrad3x3(self, ws, dy: Act, x: Act, B, S, cin, cout, gW, s, amax_dy=None, amax_x=None):
+        """Weight gradient of a 3x3 conv on the split-K GEMMs of this engine's arithmetic, folded into gW (OIHW)."""
         lb = lib()
         sp = wgrad_splits(B * S * S, cout, 9 * cin)
-        if pre is not None:        # X = relu(x s + t) of a fused producer (16-bit arithmetic, kernel-row weight gradient)
-            sums = self._producer_sums(ws, sums_of, sp) if sums_of is not None else (None, 0, None, None, None)
-            dt = 2 if (sums_of is not None and self._prod16(ws, sums_of)) else 0
-            lb.cdm_conv3x3_wgrad_x16_ex(dy.p, dy.ld, None, 0, None, None, None, None, None, None, None, cout, x.p, B, S,
-                                        S, cin, x.ld, pre[0], pre[1], *sums, amax_dy, amax_x, sp, _p(ws.slab),
-                                        self.nterm, dt, s)
-            lb.cdm_slab_reduce(_p(ws.slab), sp, cout, 9 * cin, _p(gW), 9 * cin, 1, 9, cin, 0, 1.0, s)
-            return
         if S % 8:
             # the 16-bit weight-gradient GEMMs stage 8-pixel pieces of one image row: other widths take the fp32 GEMM
             lb.cdm_conv3x3_wgrad(dy.p, dy.ld, cout, x.p, B, S, S, cin, x.ld, sp, _p(ws.slab), s)
@@ -1119,29 +1002,29 @@ class UNetEngine:
         # slab[z][co][tap*cin+ci] -> OIHW [co][ci][tap]
         lb.cdm_slab_reduce(_p(ws.slab), sp, cout, 9 * cin, _p(gW), 9 * cin, 1, 9, cin, 0, 1.0, s)
 
-    def _convT_bwd(self, ws, P, name, gy: Act, x: Act, B, Hin, cin, cout, dx: Act, G, s):
-        """ConvTranspose2d(cin, cout, 2, 2) backward; gy is the grad of its output [B, 2Hin, 2Hin, cout]."""
+    def _convT_bwd(self, ws, P, ct: ConvTSpec, G, s):
+        """ConvTranspose2d(cin, nf, 2, 2) backward; the grad of its output [B, 2Hin, 2Hin, nf] is where its consumer's
+        dgrad wrote it."""
         lb = lib()
+        name, B, Hin, cin, cout = ct.name, ws.B, ct.Hin, ct.cin, self.nf
+        gy, x, dx = ws.plan[ct.consumer.index].dgrad_dst, getattr(ws, ct.src), getattr(ws, "d" + ct.src)
         Ho = 2 * Hin
         lb.cdm_reduce_sum(gy.p, gy.ld, B, Ho * Ho, cout, CHUNK, _p(ws.slab), s)
         nparts = fold(ws, _p(ws.slab), B * _cdiv(Ho * Ho, CHUNK), 1, cout, s)
         lb.cdm_slab_sum_all(_p(ws.dpart), nparts, 1, 0, 1, cout, _p(G[name + ".bias"]), 0, 1, 0, s)
         sp = wgrad_splits(B * Hin * Hin, cin, 4 * cout)
-        x16 = self.x16
-        if x16 and Hin % 8 == 0:
-            prod = next(k for k, v in self._CONVT_GRAD_PRODUCERS.items() if v == name)
-            a_gy = self._slot(ws, "gT:" + prod)
-            a_x = self._slot(ws, {"up1.model.0": "catU1", "up2.model.0": "catU2"}[name])
-            lb.cdm_convT2x2_wgrad_x16(x.p, B, Hin, Hin, cin, x.ld, gy.p, cout, gy.ld, a_x, a_gy, sp, _p(ws.slab),
-                                      self.nterm, s)
+        if self.x16 and Hin % 8 == 0:
+            a_gy = self._slot(ws, ct.g_slot)
+            lb.cdm_convT2x2_wgrad_x16(x.p, B, Hin, Hin, cin, x.ld, gy.p, cout, gy.ld, self._slot(ws, ct.src), a_gy, sp,
+                                      _p(ws.slab), self.nterm, s)
         else:   # fp32 arithmetic, or an input grid whose width is not a multiple of 8 (the 16-bit GEMM's pieces)
             lb.cdm_convT2x2_wgrad(x.p, B, Hin, Hin, cin, x.ld, gy.p, cout, gy.ld, sp, _p(ws.slab), s)
         # slab[z][ci][ij*cout+co] -> [ci][co][ij]
         lb.cdm_slab_reduce(_p(ws.slab), sp, cin, 4 * cout, _p(G[name + ".weight"]), 4 * cout, 1, 4, cout, 0, 1.0, s)
         if self.x16:
-            a_gy = self._slot(ws, "gT:" + next(k for k, v in self._CONVT_GRAD_PRODUCERS.items() if v == name))
-            lb.cdm_convT2x2_dgrad_x16(gy.p, B, Hin, Hin, cout, gy.ld, _p(self.pk[name + ".wtT_x"]), a_gy,
-                                      self._wamax(name + ".wtT"), dx.p, dx.ld, cin, 0, self.nterm, s)
+            lb.cdm_convT2x2_dgrad_x16(gy.p, B, Hin, Hin, cout, gy.ld, _p(self.pk[name + ".wtT_x"]),
+                                      self._slot(ws, ct.g_slot), self._wamax(name + ".wtT"), dx.p, dx.ld, cin, 0,
+                                      self.nterm, s)
         else:
             lb.cdm_convT2x2_dgrad(gy.p, B, Hin, Hin, cout, gy.ld, _p(self.pk[name + ".wtT"]), dx.p, dx.ld, cin, 0, s)
 
@@ -1205,9 +1088,9 @@ def wgrad_splits(K: int, M: int, N: int) -> int:
     (768 blocks): 228 splits gave 684 blocks = 2.67 rounds, whose last round ran a third empty (same-box A/B,
     profiles/r3_ab_wgrad_rounds.txt: C2 train step 53.04 -> 51.89 ms, C4 33.09 -> 32.12 ms).  Others: ~2048
     workgroups of the generic split GEMM."""
-    if N % 9 == 0 and M % 128 == 0 and (N // 9) % 128 == 0 and os.environ.get("CDM_WGRAD_ROUNDS", "1") != "0":
+    if N % 9 == 0 and M % 128 == 0 and (N // 9) % 128 == 0:
         per = 3 * (M // 128) * ((N // 9) // 128)
-        want = max(1, min(512, round(int(os.environ.get("CDM_WGRAD_BLOCKS", "768")) / per)))
+        want = max(1, min(512, round(WGRAD_BLOCKS / per)))
         return lib().raw("cdm_gemm_splits")(K, want)
     tiles = _cdiv(M, 128) * _cdiv(N, 128)
     want = max(1, min(512, _cdiv(2048, tiles)))
@@ -1219,13 +1102,35 @@ def ctypes_addr(obj):
     return ctypes.addressof(obj)
 
 
+class LayerPlan:
+    """What the launches of one conv layer need in one workspace, resolved once (Workspace.__init__).
+
+    y, bn: the pre-norm output and the BatchNorm coefficient tensors.  src / dst: input and output activations; pre =
+    (scale, shift) pointers where a fused producer hands over its y for src (the staging applies BN + ReLU).
+    fused_fwd: this layer's own apply runs in its consumer's staging; ymm: (pointer, ld) of its max / min keys (h3).
+    Train: gout = the gradient of its output, dy its BN-backward buffer (non-fused), dgrad_dst / dgrad_accum where its
+    input gradient goes, g_slot the amax-slot key that dgrad output records into; fused: BN backward inside the dgrad;
+    sums_from: the producer's plan whose BN-backward sums this layer's weight gradient accumulates (that plan:
+    sums_by, sums_parts partials); sp: split-K factor of its weight gradient; own16: y and g stored as bf16;
+    dt_fwd / dt_dgrad / dt_wgrad: the dtype bits of its three conv launches."""
+    __slots__ = ("l", "y", "bn", "src", "pre", "dst", "fused_fwd", "ymm", "gout", "dy", "dgrad_dst", "dgrad_accum",
+                 "g_slot", "fused", "sums_from", "sums_by", "sums_parts", "sp", "own16", "dt_fwd", "dt_dgrad",
+                 "dt_wgrad")
+
+    def __init__(self, l: LayerSpec):
+        self.l = l
+        self.y = self.bn = self.src = self.pre = self.dst = self.ymm = self.gout = self.dy = self.dgrad_dst = None
+        self.g_slot = self.sums_from = None
+        self.fused_fwd = self.dgrad_accum = self.fused = self.sums_by = False
+        self.sums_parts = self.sp = self.own16 = self.dt_fwd = self.dt_dgrad = self.dt_wgrad = 0
+
+
 class Workspace:
     """All device buffers for one batch size and mode (train keeps what backward needs)."""
 
     def __init__(self, eng: UNetEngine, B: int, train: bool, frozen: bool = False):
         self.eng, self.B, self.train = eng, B, train
         self.frozen = False          # set by each forward (eval-mode BatchNorm in a train-structured forward)
-        self.zO_fused = False        # set by each forward: out.1's GroupNorm + ReLU applied inside out.3's kernels
         dev = eng.device
         nf, H, ncf = eng.nf, eng.H, eng.ncf
         H1, H2 = H // 2, H // 4
@@ -1240,7 +1145,7 @@ class Workspace:
         self.y0 = E(P2, 2 * nf)
         self.yO = E(P0, nf)
         # zO = relu(GN(yO)) only exists where out.3 cannot apply out.1 in its staging (537 MB at the bench shape)
-        self.zO = E(P0, nf) if not eng.fuses_gn_out(train) else torch.empty(0, device=dev)
+        self.zO = E(P0, nf) if not eng.fuses_gn_out() else torch.empty(0, device=dev)
         self.hsum, self.hpre, self.hv = E(B, 2 * nf), E(B, 2 * nf), E(B, 2 * nf)
         self.c_zero = torch.zeros(B, ncf, device=dev)
         self.emb = {m: E(B, (2 if m.endswith("1") else 1) * nf) for m in MLPS}
@@ -1252,174 +1157,144 @@ class Workspace:
             self.d_emb_row = {m: E(1, (2 if m.endswith("1") else 1) * nf) for m in MLPS}   # broadcast t / c
         self.gn0 = {k: E(B * 2 * nf) for k in ("mean", "invstd", "scale", "shift")}
         self.gnO = {k: E(B * nf) for k in ("mean", "invstd", "scale", "shift")}
-        # per conv-BN layer: y (pre-norm), z destinations, BN coefficients
+        # per conv-BN layer: its plan — y (pre-norm), BN coefficients, source and destination
         L = eng.layers
-        self.y, self.src, self.dst, self.dst_kind, self.bn = {}, {}, {}, {}, {}
+        self.plan = [LayerPlan(l) for l in L]
         self._no_z = torch.empty(0, device=dev)
-        z = {}
-        for l in L:
-            npx = B * l.S * l.S
-            self.y[l.name] = E(npx, l.cout)
-            self.bn[l.name] = {k: E(l.cout) for k in ("mean", "invstd", "scale", "shift")}
-        names = [l.name for l in L]
-        # destinations of each layer's activation output
-        kinds = {}
-        for i, l in enumerate(L):
-            kinds[l.name] = "dense"
-        kinds["init_conv.conv2"] = "resid"
-        kinds["down1.model.1.conv2"] = "pool"
-        kinds["down2.model.1.conv2"] = "pool"
-        kinds["up1.model.2.conv2"] = "film"
-        kinds["up2.model.2.conv2"] = "plain"
-        self.dst_kind = kinds
-        self.fused_fwd = {l.name for l in L if train and eng.fuses_bn_fwd(l, kinds[l.name], B)}
-        for l in L:
-            k = kinds[l.name]
-            if k == "dense":
-                # a fused producer's z is never materialised (the consumer stages relu(y s + t) itself)
-                z[l.name] = Act(E(B * l.S * l.S, l.cout) if l.name not in self.fused_fwd else self._no_z, l.cout)
-                self.dst[l.name] = z[l.name]
-        self.dst["init_conv.conv2"] = self.catO.sl(nf, nf)
-        self.dst["down1.model.1.conv2"] = self.catU2.sl(nf, nf)
-        self.dst["down2.model.1.conv2"] = self.catU1.sl(2 * nf, 2 * nf)
-        self.dst["up1.model.2.conv2"] = self.catU2.sl(0, nf)
-        self.dst["up2.model.2.conv2"] = self.catO.sl(0, nf)
-        # inputs of each conv
-        prev = {names[i]: names[i - 1] for i in range(1, len(names))}
-        for l in L:
-            if l.name == "init_conv.conv1":
-                self.src[l.name] = None
-            elif l.name == "down1.model.0.conv1":
-                self.src[l.name] = self.catO.sl(nf, nf)
-            elif l.name == "down2.model.0.conv1":
-                self.src[l.name] = self.catU2.sl(nf, nf)
-            elif l.name == "up1.model.1.conv1":
-                self.src[l.name] = Act(self.yT1, nf)
-            elif l.name == "up2.model.1.conv1":
-                self.src[l.name] = Act(self.yT2, nf)
-            else:
-                self.src[l.name] = self.dst[prev[l.name]]
+        for p in self.plan:
+            p.y = E(B * p.l.S * p.l.S, p.l.cout)
+            p.bn = {k: E(p.l.cout) for k in ("mean", "invstd", "scale", "shift")}
+        self.y = {p.l.name: p.y for p in self.plan}
+        self.bn = {p.l.name: p.bn for p in self.plan}
+        self.dst_kind = {l.name: l.kind for l in L}
+        self.fused_fwd = {l.name for l in L if train and eng.fuses_bn_fwd(l, l.kind, B)}
+        for p in self.plan:
+            l = p.l
+            p.fused_fwd = l.name in self.fused_fwd
+            if l.dst is not None:
+                p.dst = self._view(l.dst)
+            else:      # a fused producer's z is never materialised (the consumer stages relu(y s + t) itself)
+                p.dst = Act(self._no_z if p.fused_fwd else E(B * l.S * l.S, l.cout), l.cout)
+            if l.src is not None:
+                p.src = self._view(l.src)
+            elif l.prev is not None:                 # (layer 0 reads the image: cdm_conv3x3_cin1_*, or set per forward)
+                q = self.plan[l.prev.index]
+                p.src = q.dst
+                if q.fused_fwd:                      # the producer hands over its pre-norm output and (scale, shift)
+                    p.src, p.pre = Act(q.y, l.cin), (_p(q.bn["scale"]), _p(q.bn["shift"]))
+        self.dst = {p.l.name: p.dst for p in self.plan}     # by name, like y and bn (tools, tests)
         self.slab = E(self._slab_floats())
-        # per fused layer: max / min keys of its pre-norm output ([2][n_fused][Cmax] int32, refilled every forward)
-        self._ymm_idx = {n: i for i, n in enumerate(sorted(self.fused_fwd))}
-        self._ymm_C = max([l.cout for l in L] + [1])
-        self.ymm = torch.empty(2 * max(1, len(self.fused_fwd)) * self._ymm_C, dtype=torch.int32, device=dev)
+        # per fused layer: max / min keys of its pre-norm output ([2][n_fused][Cmax] int32, refilled every forward):
+        # p.ymm = (pointer, ld) of the layer's max keys; its min keys sit ld ints further
+        Cmax = max(l.cout for l in L)
+        self.ymm = torch.empty(2 * max(1, len(self.fused_fwd)) * Cmax, dtype=torch.int32, device=dev)
+        if eng.h3:
+            for i, p in enumerate(sorted((p for p in self.plan if p.fused_fwd), key=lambda p: p.l.name)):
+                p.ymm = (self.ymm.data_ptr() + 4 * i * Cmax, self.ymm.numel() // 2)
         self.amax = torch.zeros(192, device=dev)  # h3 operand maxima, one slot per producer (UNetEngine._slot)
         self.aslot = {}
         self.dpart = torch.empty(10 * 32768 + 4096, device=dev, dtype=torch.float64)
         self.sc_pending = None
-        if train:
-            C4 = 4 * nf
-            self.G0, self.D0 = E(P0, 2 * nf), E(P0, 2 * nf)
-            self.G1, self.D1 = E(P1, 2 * nf), E(P1, 2 * nf)
-            self.D2 = E(P2, 4 * nf)
-            self.gT1, self.gT2 = self.G1, self.G0
-            self.dcatO = Act(E(P0, 2 * nf), 2 * nf)
-            self.dcatU2 = Act(E(P1, 2 * nf), 2 * nf)
-            self.dcatU1 = Act(E(P2, 4 * nf), 4 * nf)
-            self.dhv = E(B, 2 * nf)
-            self.up0T = E(P2, 2 * nf) if eng.up0_large else None   # dy0 with (co, ij) order (large up0)
-            self.coef = [E(C4) for _ in range(3)]
-            self.gcoef = [E(B * C4) for _ in range(6)]
-            # backward wiring: grad of each layer's output (gout), its dy buffer and dgrad destination
-            self.gout, self.dy, self.dgrad_dst, self.dgrad_accum = {}, {}, {}, {}
-            for l in L:
-                Gb = self.G0 if l.S == H else self.G1
-                Db = self.D0 if l.S == H else self.D1
-                self.dy[l.name] = Act(Db, l.cout)
-                k = kinds[l.name]
-                if k == "resid":
-                    self.gout[l.name] = self.dcatO.sl(nf, nf)
-                elif k == "pool":
-                    self.gout[l.name] = (self.dcatU2.sl(nf, nf) if l.name.startswith("down1")
-                                         else self.dcatU1.sl(2 * nf, 2 * nf))
-                elif k == "film":
-                    self.gout[l.name] = self.dcatU2.sl(0, nf)
-                elif k == "plain":
-                    self.gout[l.name] = self.dcatO.sl(0, nf)
-                else:
-                    self.gout[l.name] = Act(Gb, l.cout)   # written by the next layer's dgrad
-                # where this layer's dgrad (grad wrt its input) goes
-                if l.name == "down1.model.0.conv1":
-                    self.dgrad_dst[l.name], self.dgrad_accum[l.name] = self.dcatO.sl(nf, nf), True
-                elif l.name == "down2.model.0.conv1":
-                    self.dgrad_dst[l.name], self.dgrad_accum[l.name] = self.dcatU2.sl(nf, nf), True
-                elif l.name in ("up1.model.1.conv1", "up2.model.1.conv1"):
-                    self.dgrad_dst[l.name], self.dgrad_accum[l.name] = Act(Gb, l.cin), False
-                elif l.cin > 1:
-                    self.dgrad_dst[l.name], self.dgrad_accum[l.name] = Act(Gb, l.cin), False
-            self._wire_fused_bn_bwd(eng, L, kinds)
-            # the fused layers' dy (eng.dy_store): one buffer, rewritten by each fused layer's dgrad and read by its
-            # weight gradient right after; g's row stride (fp32 size, bf16 dy use half)
-            self.dyo = None
-            if eng.dy_store and self.fused:
-                self.dyo = E(max(B * l.S * l.S * self.gout[l.name].ld for l in L if l.name in self.fused))
-            # producer BN-backward sums in the consumer's weight gradient: a fused (BN-ReLU staged) dense producer p
-            # whose consumer c takes the kernel-row weight gradient with the X transform
-            self.sums_from, self.sums_by, self.sums_sp = {}, {}, {}
-            if eng.fuse_bn_sums:
-                for i in range(1, len(L)):
-                    p_, c_ = L[i - 1], L[i]
-                    if p_.name in self.fused_fwd and kinds[p_.name] == "dense" and c_.cin % 128 == 0 \
-                            and c_.cout % 128 == 0 and c_.S % 16 == 0:
-                        self.sums_from[c_.name], self.sums_by[p_.name] = p_.name, c_.name
-            nsum = max([wgrad_splits(B * L[i].S * L[i].S, L[i].cout, 9 * L[i].cin) * 3 * (L[i].cout // 128) * 5
-                        * L[i].cin for i in range(len(L)) if L[i].name in self.sums_from] + [1])
-            self.sums = E(nsum)
-            # bf16 activations (C4): the fused chain's y and g (layers whose BN-ReLU apply runs in the next conv's
-            # staging, C_in > 1; each has its BN-backward sums fused into the consumer's weight gradient and a private
-            # gradient buffer, so every kernel reading them is one of the two templated conv kernels)
-            self.act16 = set()
-            if eng.act16 and not frozen:
-                self.act16 = {l.name for l in L if l.name in self.fused_fwd and l.cin > 1 and l.name in self.sums_by
-                              and l.name in self.fused and self.gout[l.name].off == 0}
-        else:
-            self.fused, self.g_amax_key, self.out0_g_key = set(), {}, None
-            self.sums_from, self.sums_by, self.sums_sp = {}, {}, {}
-            self.act16 = set()
-            self.dyo = None
+        self.fused, self.out0_g_key, self.sums_from, self.act16, self.dyo = set(), None, {}, set(), None
+        if not train:
+            return
+        C4 = 4 * nf
+        self.G0, self.D0 = E(P0, 2 * nf), E(P0, 2 * nf)
+        self.G1, self.D1 = E(P1, 2 * nf), E(P1, 2 * nf)
+        self.D2 = E(P2, 4 * nf)
+        self.dcatO = Act(E(P0, 2 * nf), 2 * nf)
+        self.dcatU2 = Act(E(P1, 2 * nf), 2 * nf)
+        self.dcatU1 = Act(E(P2, 4 * nf), 4 * nf)
+        self.dhv = E(B, 2 * nf)
+        self.up0T = E(P2, 2 * nf) if eng.up0_large else None   # dy0 with (co, ij) order (large up0)
+        self.coef = [E(C4) for _ in range(3)]
+        self.gcoef = [E(B * C4) for _ in range(6)]
+        # backward wiring: the grad of each layer's output (gout: the dcat* slice of a cat* destination, else written
+        # by the next layer's dgrad), its dy buffer and where its own dgrad goes (accumulating into the dcat* slice of a
+        # cat* source: the skip connection's other gradient is already there)
+        pairs = {H: (self.G0, self.D0), H1: (self.G1, self.D1)}
+        for p in self.plan:
+            l = p.l
+            Gb, Db = pairs[l.S]
+            p.dy = Act(Db, l.cout)
+            p.gout = self._view(l.dst, grad=True) if l.dst is not None else Act(Gb, l.cout)
+            if l.src is not None and l.src[0].startswith("cat"):
+                p.dgrad_dst, p.dgrad_accum = self._view(l.src, grad=True), True
+            elif l.cin > 1:
+                p.dgrad_dst = Act(Gb, l.cin)
+            if l.cin > 1:
+                p.sp = wgrad_splits(B * l.S * l.S, l.cout, 9 * l.cin)
+        for ct in eng.convT:       # the grad wrt a ConvT output also records its max, for the h3 ConvT backward
+            self.plan[ct.consumer.index].g_slot = ct.g_slot
+        self._wire_fused_bn_bwd(pairs)
+        # the fused layers' dy: one buffer, rewritten by each fused layer's dgrad and read by its weight gradient
+        # right after; g's row stride (fp32 size, bf16 dy use half)
+        if self.fused:
+            self.dyo = E(max(B * p.l.S * p.l.S * p.gout.ld for p in self.plan if p.fused))
+        # producer BN-backward sums in the consumer's weight gradient: a fused (BN-ReLU staged) dense producer q
+        # whose consumer p takes the kernel-row weight gradient with the X transform; one partial per block of that
+        # weight gradient: split x kernel row x co tile
+        if eng.fuse_bn_sums:
+            for p in self.plan[1:]:
+                q, c = self.plan[p.l.index - 1], p.l
+                if q.fused_fwd and c.cin % 128 == 0 and c.cout % 128 == 0 and c.S % 16 == 0:
+                    p.sums_from, q.sums_by, q.sums_parts = q, True, p.sp * 3 * (c.cout // 128)
+                    self.sums_from[c.name] = q.l.name
+        self.sums = E(max([p.sums_from.sums_parts * 5 * p.l.cin for p in self.plan if p.sums_from] + [1]))
+        # bf16 activations (C4): the fused chain's y and g (layers whose BN-ReLU apply runs in the next conv's
+        # staging, C_in > 1; each has its BN-backward sums fused into the consumer's weight gradient and a private
+        # gradient buffer, so every kernel reading them is one of the two templated conv kernels)
+        if eng.act16 and not frozen:
+            self.act16 = {p.l.name for p in self.plan if p.fused_fwd and p.l.cin > 1 and p.sums_by and p.fused
+                          and p.gout.off == 0}
+        # dtype bits of the launches (include/cdm_hip.h, "dt"): a layer in act16 stores y and g as bf16; its consumer
+        # stages that y (forward, weight-gradient X) and writes that g (dgrad output, unless it accumulates elsewhere)
+        for p in self.plan:
+            q = self.plan[p.l.index - 1] if p.l.index else None
+            p.own16 = int(p.l.name in self.act16)
+            prod16 = q.own16 if q is not None else 0
+            out16 = prod16 if (prod16 and not p.dgrad_accum and p.dgrad_dst.buf is q.gout.buf) else 0
+            p.dt_fwd = prod16 | (p.own16 << 1)
+            p.dt_dgrad = p.own16 | (out16 << 1)
+            p.dt_wgrad = p.own16 | (prod16 << 1)
 
-    def ymm_of(self, l) -> tuple:
-        """(pointer, ld) of fused layer l's max keys; its min keys sit ld ints further."""
-        half = self.ymm.numel() // 2
-        return self.ymm.data_ptr() + 4 * self._ymm_idx[l.name] * self._ymm_C, half
+    def _view(self, sym, grad: bool = False) -> Act:
+        """The activation view a LayerSpec names as (buffer, first channel, channels) in units of n_feat; grad: the same
+        slice of the buffer's gradient."""
+        name, c0, C = sym
+        nf, b = self.eng.nf, getattr(self, "d" + name if grad else name)
+        return b.sl(c0 * nf, C * nf) if isinstance(b, Act) else Act(b, C * nf)
 
-    def _wire_fused_bn_bwd(self, eng, L, kinds):
+    def _wire_fused_bn_bwd(self, pairs):
         """Fused layers read g and write their dgrad without a dy buffer in between, so g and the dgrad output
         must differ: walking the backward order, each fused layer writes its dgrad into the other buffer of its
-        resolution's pair (G, D), which becomes the g of the layer before it.  Non-fused layers keep dy in D
-        (in place when their g already sits in D: the mode-0 apply is elementwise, index for index)."""
-        self.fused = {l.name for l in L if eng.fuses_bn_bwd(l, kinds[l.name], self.B)}
-        self.g_amax_key = {}
-        self.out0_g_key = None
-        if not self.fused:
-            return
-        other = {}
-        for a_, b_ in ((self.G0, self.D0), (self.G1, self.D1)):
-            other[a_.data_ptr()], other[b_.data_ptr()] = b_, a_
-        idx = {l.name: i for i, l in enumerate(L)}
-        for l in reversed(L):
-            if l.name not in self.fused:
+        resolution's pair (G, D), which becomes the g of the layer before it (or of the ConvT that feeds it).  Non-fused
+        layers keep dy in D (in place when their g already sits in D: the mode-0 apply is elementwise, index for
+        index).  The dgrad that writes a fused layer's g (the next layer's; out.0's for the last) records max|g| for
+        the layer's dy bound."""
+        eng = self.eng
+        self.fused = {l.name for l in eng.layers if eng.fuses_bn_bwd(l, l.kind, self.B)}
+        for p in reversed(self.plan):
+            l = p.l
+            p.fused = l.name in self.fused
+            if not p.fused:
                 continue
-            if idx[l.name] + 1 < len(L):
-                nxt = L[idx[l.name] + 1]                  # its g is written (last) by the next layer's dgrad
-                self.g_amax_key[nxt.name] = "g:" + l.name
-            else:                                         # up2's last conv ("plain"): g is out.0's dgrad output
-                self.out0_g_key = "g:" + l.name
-            g = self.gout[l.name]
-            if l.name in ("down1.model.0.conv1", "down2.model.0.conv1"):
-                continue                                  # dgrad accumulates into a concat-grad slice
-            # g of a "plain" / "resid" layer is a slice of the concat gradient: any buffer of the pair is free
-            dst = other.get(g.buf.data_ptr(), self.G0 if l.S == self.eng.H else self.G1)
-            self.dgrad_dst[l.name] = Act(dst, l.cin)
-            if l.name == "up1.model.1.conv1":
-                self.gT1 = dst
-            elif l.name == "up2.model.1.conv1":
-                self.gT2 = dst
+            if l.next is not None:
+                nxt = self.plan[l.next.index]
+                assert nxt.g_slot is None
+                nxt.g_slot = "g:" + l.name
             else:
-                prev = L[idx[l.name] - 1]
-                assert kinds[prev.name] == "dense", prev.name
-                self.gout[prev.name] = Act(dst, prev.cout)
+                self.out0_g_key = "g:" + l.name
+            if p.dgrad_accum:
+                continue                                  # the dgrad accumulates into a concat-grad slice
+            # g of a "plain" / "resid" layer is a slice of the concat gradient: any buffer of the pair is free
+            G_, D_ = pairs[l.S]
+            dst = D_ if p.gout.buf is G_ else G_
+            p.dgrad_dst = Act(dst, l.cin)
+            if l.src is None:
+                assert l.prev.kind == "dense", l.prev.name
+                self.plan[l.prev.index].gout = Act(dst, l.cin)
+
 
     def _slab_floats(self):
         eng, B = self.eng, self.B

@@ -1,19 +1,24 @@
 """CPU dry run of the engine's launch sequence (no GPU): every library call of a train forward + backward is
-recorded through a stand-in for the C-ABI library, then checked on the host — every pointer argument lies in a
-live tensor of the run, and every split-K slab / fused-BN operand range fits its buffer.  Catches workspace
-sizing and wiring errors before a kernel can fault on the GPU (the out.0 weight-gradient slab was once sized
-only by the 18 BN layers: fine at B=256, an overflow at B=2, n_feat=128)."""
+recorded through a stand-in for the C-ABI library (tools/engine_trace.py), then checked on the host — every pointer
+argument lies in a live tensor of the run, and every split-K slab / fused-BN operand range fits its buffer.  Catches
+workspace sizing and wiring errors before a kernel can fault on the GPU (the out.0 weight-gradient slab was once sized
+only by the 18 BN layers: fine at B=256, an overflow at B=2, n_feat=128).  Every operand-extent block counts its hits,
+and the configurations that must take a path assert a count above zero: a renamed entry point cannot switch its
+check off."""
+import collections
 import ctypes
+import importlib.util
 import os
 import re
 
 import pytest
-import torch
 
-import cdm_amd._lib as LL
-import cdm_amd.engine as E
-
-HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cdm_hip.h")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = os.path.join(ROOT, "include", "cdm_hip.h")
+_spec = importlib.util.spec_from_file_location("engine_trace", os.path.join(ROOT, "tools", "engine_trace.py"))
+T = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(T)
+_eff_splits = T.eff_splits
 
 
 def _param_names():
@@ -24,98 +29,65 @@ def _param_names():
     return out
 
 
-def _eff_splits(K, s, bk=16):
-    kt = (K + bk - 1) // bk
-    s = max(1, min(s, kt))
-    per = (kt + s - 1) // s
-    return (kt + per - 1) // per if kt > 0 else 1
-
-
-class _Recorder:
-    def __init__(self, protos):
-        self.protos, self.calls = protos, []
-
-    def __getattr__(self, name):
-        if name in self.protos:
-            return lambda *a: self.calls.append((name, a)) or 0
-        if name == "raw":
-            return lambda n: (lambda K, s: _eff_splits(K, s)) if n == "cdm_gemm_splits" else (lambda *a: 0)
-        raise AttributeError(name)
-
-
-def _dry_run(monkeypatch, nf, B, math, H=64, train=True):
-    protos = LL.parse_header()
-    rec = _Recorder(protos)
-    monkeypatch.setattr(E, "lib", lambda: rec)
-    eng = E.UNetEngine(nf, 6, H, "cpu", math)
+def _dry_run(nf, B, math, H=64, train=True, in_channels=1, frozen=False):
+    rec, live, eng, _ = T.dry_run(nf, B, math, H, train, in_channels, frozen)
     _dry_run.last_eng = eng
-    from cdm_amd.model import ContextUnet
-    torch.manual_seed(0)
-    m = ContextUnet(1, nf, 6, H, conv_math=math)
-    P = {k: v.detach().clone() for k, v in list(m.named_parameters()) + list(m.named_buffers())}
-    eng.repack(P, train, 0)
-    ws = eng.workspace(B, train)
-    x, t, c = torch.empty(B, H, H), torch.rand(B), torch.rand(B, 6)
-    sc_w, sc_b = torch.rand(2 * nf), torch.rand(2 * nf)
-    eng.forward(ws, P, x, t if train else t[:1], c, sc_w, sc_b, B if train else B // 2, 0)
-    G = {n: torch.empty_like(v) for n, v in m.named_parameters()}
-    deps = torch.empty(B, H, H)
-    if train:
-        eng.backward(ws, P, deps, G, 0)
-    live = []
-
-    def reg(o):
-        if isinstance(o, torch.Tensor) and o.numel():
-            live.append((o.data_ptr(), o.data_ptr() + o.numel() * o.element_size()))
-        elif isinstance(o, E.Act):
-            reg(o.buf)
-        elif isinstance(o, dict):
-            for v in o.values():
-                reg(v)
-        elif isinstance(o, (list, tuple)):
-            for v in o:
-                reg(v)
-    for o in (P, G, eng.pk, vars(ws), [x, t, c, sc_w, sc_b, deps, eng._amax, eng._ones, eng._zeros],
-              [getattr(eng, "_batch_jobs", None), getattr(eng, "_batch_slots", None)]):
-        reg(o)
-    return rec.calls, protos, live
-
-
-def _region(live, p):
-    for a, b in live:
-        if a <= p < b:
-            return a, b
-    return None
+    return rec.calls, rec.protos, live
 
 
 # The bench shapes run at full size: the workspaces are torch.empty on the host, which the kernel commits only when
 # touched, so B=256 (~20 GB of address space) costs < 1 GB of RSS.  Train: C2 (n_feat=128, B=256), C5 (n_feat=256,
-# 256x256, B=16); eval (sampler): the CFG batch of C2 (2 x 256 images, cond + uncond halves).
-@pytest.mark.parametrize("nf,B,math,H,train", [(128, 2, "h3", 64, True), (128, 3, "fp32", 64, True),
-                                               (64, 2, "h3", 64, True), (16, 1, "x6", 64, True),
-                                               (128, 256, "h3", 64, True), (128, 256, "bf16", 64, True),
-                                               (128, 1, "h3", 256, True), (256, 16, "h3", 256, True),
-                                               (16, 20, "h3", 256, True),
-                                               (128, 512, "h3", 64, False), (256, 32, "h3", 256, False)])
-def test_launch_arguments_stay_in_bounds(monkeypatch, nf, B, math, H, train):
-    calls, protos, live = _dry_run(monkeypatch, nf, B, math, H, train)
+# 256x256, B=16); eval (sampler): the CFG batch of C2 (2 x 256 images, cond + uncond halves).  in_channels = 3 runs
+# the general kernels on the padded image; frozen = the forward / backward of model.eval() under autograd; H = 20: the
+# generic-kernel widths.  `must`: the extent blocks the configuration has to reach.
+TRAIN_H3 = ("fwd_ex", "wgrad_ex", "dgrad_bnbwd_dy", "dy_out", "x_g", "x_sums")
+TRAIN_BF16 = ("fwd_ex", "wgrad_ex", "bn_bwd_dy", "x_g", "x_sums", "bf16")
+CASES = [
+    (128, 2, "h3", 64, True, 1, False, TRAIN_H3), (128, 3, "fp32", 64, True, 1, False, ()),
+    (64, 2, "h3", 64, True, 1, False, ()), (16, 1, "x6", 64, True, 1, False, ()),
+    (128, 256, "h3", 64, True, 1, False, TRAIN_H3), (128, 256, "bf16", 64, True, 1, False, TRAIN_BF16),
+    (128, 1, "h3", 256, True, 1, False, ()), (256, 16, "h3", 256, True, 1, False, ()),
+    (16, 20, "h3", 256, True, 1, False, ()),
+    (128, 512, "h3", 64, False, 1, False, ("fwd_fused", "fused_pool")), (256, 32, "h3", 256, False, 1, False, ()),
+    (16, 2, "h3", 64, True, 3, False, ()), (128, 2, "bf16", 64, True, 3, False, TRAIN_BF16),
+    (128, 2, "bf16", 64, True, 1, True, ("fwd_ex", "wgrad_ex", "bn_bwd_dy", "x_g", "x_sums")),
+    (16, 2, "h3", 20, True, 1, False, ()),
+]
+
+
+def _case_id(c):
+    return "-".join(str(v) for v in c[:5]) + ("-c%d" % c[5] if c[5] > 1 else "") + ("-frozen" if c[6] else "")
+
+
+@pytest.mark.parametrize("nf,B,math,H,train,in_channels,frozen,must", CASES, ids=[_case_id(c) for c in CASES])
+def test_launch_arguments_stay_in_bounds(nf, B, math, H, train, in_channels, frozen, must):
+    calls, protos, live = _dry_run(nf, B, math, H, train, in_channels, frozen)
     names = _param_names()
     assert len(calls) > (100 if train else 40)
     problems = []
+    hits = collections.Counter()
 
     def need(name, a, ptr, nbytes, what):
-        r = _region(live, ptr)
+        r = T.region(live, ptr)
         if r is None:
             problems.append(f"{name}: {what} not in a live tensor")
         elif ptr + nbytes > r[1]:
             problems.append(f"{name}: {what} overruns its buffer by {ptr + nbytes - r[1]} bytes")
+
+    def rows(name, a, key, npix, ld, C, esz=4):
+        """an activation operand: npix rows of C elements (esz bytes each) at a row stride of ld elements"""
+        need(name, a, a[key], ((npix - 1) * a[ld] + a[C]) * esz, key)
+
+    def vecs(name, a, keys, C):
+        for k in keys:
+            need(name, a, a[k], a[C] * 4, k)
 
     for name, args in calls:
         pn = names[name]
         a = dict(zip(pn, args))
         for (pname, v), ty in zip(zip(pn, args), protos[name]):
             if ty is ctypes.c_void_p and isinstance(v, int) and v and name not in ("cdm_embed_fwd", "cdm_embed_bwd"):
-                if _region(live, v) is None:
+                if T.region(live, v) is None:
                     problems.append(f"{name}: pointer {pname} not in a live tensor")
         if name.startswith("cdm_conv3x3_wgrad"):
             K = a["N"] * a["H"] * a["W"]
@@ -146,36 +118,74 @@ def test_launch_arguments_stay_in_bounds(monkeypatch, nf, B, math, H, train):
                 if wd:
                     need(name, a, wd, -(-9 * cout // 16) * 3 * cin * 16 * 2, f"job {j} wdg_x")
                 need(name, a, am, 4, f"job {j} amax")
-        if name == "cdm_conv3x3_fwd_h3_ex":
-            Pn = a["N"] * a["H"] * a["W"]
-            need(name, a, a["x"], ((Pn - 1) * a["ldx"] + a["Cin"]) * 4, "x")
-            need(name, a, a["y"], ((Pn - 1) * a["ldy"] + a["Cout"]) * 4, "y")
+        # element sizes from the dt bits (include/cdm_hip.h): forward / dgrad: bit 0 the source, bit 1 the output;
+        # weight gradient: bit 0 g / dy / y, bit 1 x / x_g
+        dt = a.get("dt", 0)
+        e0, e1 = (2 if dt & 1 else 4), (2 if dt & 2 else 4)
+        Pn = a["N"] * a["H"] * a["W"] if {"N", "H", "W"} <= a.keys() else 0
+        if dt:
+            hits["bf16"] += 1
+        if name in ("cdm_conv3x3_fwd_x16", "cdm_conv3x3_fwd_x16_ex"):
+            rows(name, a, "x", Pn, "ldx", "Cin", e0)
+            rows(name, a, "y", Pn, "ldy", "Cout", e1)
+        if name == "cdm_conv3x3_fwd_x16_ex":
+            hits["fwd_ex"] += 1
             if a["pre_s"]:
-                need(name, a, a["pre_s"], a["Cin"] * 4, "pre_s"); need(name, a, a["pre_t"], a["Cin"] * 4, "pre_t")
+                vecs(name, a, ("pre_s", "pre_t"), "Cin")
             if a["ymm"]:
                 need(name, a, a["ymm"], a["Cout"] * 4, "ymm max")
                 need(name, a, a["ymm"] + 4 * a["ymm_ld"], a["Cout"] * 4, "ymm min")
-        if name == "cdm_conv3x3_wgrad_h3_ex":
-            Pn = a["N"] * a["H"] * a["W"]
-            need(name, a, a["g"], ((Pn - 1) * a["ldg"] + a["Cout"]) * 4, "g")
+        if name == "cdm_conv3x3_wgrad_x16_ex":
+            hits["wgrad_ex"] += 1
+            rows(name, a, "g", Pn, "ldg", "Cout", e0)
             if a["y"]:
-                need(name, a, a["y"], ((Pn - 1) * a["ldy"] + a["Cout"]) * 4, "y")
-            need(name, a, a["x"], ((Pn - 1) * a["ldx"] + a["Cin"]) * 4, "x")
+                rows(name, a, "y", Pn, "ldy", "Cout", e0)
+            rows(name, a, "x", Pn, "ldx", "Cin", e1)
             if a["x_s"]:
-                need(name, a, a["x_s"], a["Cin"] * 4, "x_s"); need(name, a, a["x_t"], a["Cin"] * 4, "x_t")
-            K = a["N"] * a["H"] * a["W"]
-            need(name, a, a["slab"], _eff_splits(K, a["splits"]) * a["Cout"] * 9 * a["Cin"] * 4, "slab")
+                vecs(name, a, ("x_s", "x_t"), "Cin")
+            if a["x_g"]:
+                hits["x_g"] += 1
+                rows(name, a, "x_g", Pn, "ldxg", "Cin", e1)
+            if a["x_sums"]:
+                hits["x_sums"] += 1
+                vecs(name, a, ("x_mean", "x_invstd"), "Cin")
+                need(name, a, a["x_sums"], _eff_splits(Pn, a["splits"]) * 3 * (a["Cout"] // 128) * 5 * a["Cin"] * 4,
+                     "x_sums")
         if name == "cdm_bn_fwd_finalize" and a["ymm"]:
             need(name, a, a["ymm"], a["C"] * 4, "ymm max")
             need(name, a, a["ymm"] + 4 * a["ymm_ld"], a["C"] * 4, "ymm min")
-        if name == "cdm_conv3x3_dgrad_h3_bnbwd":
-            Pn = a["N"] * a["H"] * a["W"]
-            need(name, a, a["g"], ((Pn - 1) * a["ldg"] + a["C"]) * 4, "g")
-            need(name, a, a["y"], ((Pn - 1) * a["ldy"] + a["C"]) * 4, "y")
-            need(name, a, a["out"], ((Pn - 1) * a["ldo"] + a["Cout"]) * 4, "out")
-        if name == "cdm_conv3x3_wgrad_h3_bnbwd":
-            Pn = a["N"] * a["H"] * a["W"]
-            need(name, a, a["g"], ((Pn - 1) * a["ldg"] + a["Cout"]) * 4, "g")
-            need(name, a, a["y"], ((Pn - 1) * a["ldy"] + a["Cout"]) * 4, "y")
-            need(name, a, a["x"], ((Pn - 1) * a["ldx"] + a["Cin"]) * 4, "x")
+        if name == "cdm_conv3x3_dgrad_x16_bnbwd_dy":
+            hits["dgrad_bnbwd_dy"] += 1
+            rows(name, a, "g", Pn, "ldg", "C", e0)
+            rows(name, a, "y", Pn, "ldy", "C", e0)
+            vecs(name, a, ("s", "t", "mean", "invstd", "A", "B", "Cc"), "C")
+            rows(name, a, "out", Pn, "ldo", "Cout", e1)
+            if a["dy_out"]:
+                hits["dy_out"] += 1
+                rows(name, a, "dy_out", Pn, "ldg", "C", e0)
+        if name == "cdm_bn_bwd_dy":
+            hits["bn_bwd_dy"] += 1
+            rows(name, a, "g", a["P"], "ldg", "C", e0)
+            rows(name, a, "y", a["P"], "ldy", "C", e0)
+            vecs(name, a, ("s", "t", "mean", "invstd", "A", "B", "Cc"), "C")
+            rows(name, a, "dy", a["P"], "lddy", "C", e1)
+        if name == "cdm_conv3x3_fwd_x16_fused":
+            hits["fwd_fused"] += 1
+            rows(name, a, "x", Pn, "ldx", "Cin")
+            need(name, a, a["bias"], a["Cout"] * 4, "bias")
+            if a["kind"] == 3:      # the pooled map [N][H/2][W/2]
+                hits["fused_pool"] += 1
+                rows(name, a, "y", a["N"] * (a["H"] // 2) * (a["W"] // 2), "ldy", "Cout")
+            else:
+                rows(name, a, "y", Pn, "ldy", "Cout")
+            if a["kind"] == 1:
+                need(name, a, a["sc_x"], Pn * 4, "sc_x")
+                ndraw = 2 if a["split"] < a["N"] else 1
+                need(name, a, a["sc_w"], ndraw * a["Cout"] * 4, "sc_w")
+                need(name, a, a["sc_b"], ndraw * a["Cout"] * 4, "sc_b")
+            if a["kind"] == 2:
+                need(name, a, a["fa"], ((a["N"] - 1) * a["fan"] + a["Cout"]) * 4, "fa")
+                need(name, a, a["fb"], ((a["N"] - 1) * a["fbn"] + a["Cout"]) * 4, "fb")
     assert not problems, problems[:10]
+    missed = [k for k in must if not hits[k]]
+    assert not missed, f"extent checks that never ran: {missed} (hits {dict(hits)})"
