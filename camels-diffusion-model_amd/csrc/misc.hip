@@ -916,6 +916,86 @@ __global__ __launch_bounds__(256) void mse_accum_kernel(const float* pred, const
     }
 }
 
+static __device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Parameter scan (likelihood.ParamScan): one map scored under K candidate contexts on common noise.
+// Prologue of a scan step, table-driven: the device counter holds the position p = 0..npos-1, counting up, and a
+// timestep may repeat (pos_t[p], any value of 1..T at any position; npos is not bounded by T, which is why this is not
+// sample_prologue_kernel):  p = *ctr; *ctr = p + 1; cur_p = p; cur_i = i = pos_t[p]; t_cur = (float)((double)i / T);
+// shortcut row p.  A counter outside 0..npos-1, or an i outside 1..T, sets cur_i = 0 and touches nothing else: the
+// scan kernels of that step then write nothing.
+__global__ void scan_prologue_kernel(int* ctr, int npos, int T, const int* pos_t, int* cur_i, int* cur_p, float* t_cur,
+                                     const float* sc_table, int sc_row, float* sc_cur) {
+    const int p = *ctr;
+    __syncthreads();
+    const int i = (p >= 0 && p < npos) ? pos_t[p] : 0;
+    if (i < 1 || i > T) {
+        if (threadIdx.x == 0) *cur_i = 0;
+        return;
+    }
+    if (threadIdx.x == 0) { *ctr = p + 1; *cur_p = p; *cur_i = i; *t_cur = (float)((double)i / (double)T); }
+    if (sc_table)
+        for (int q = threadIdx.x; q < sc_row; q += blockDim.x) sc_cur[q] = sc_table[(long long)p * sc_row + q];
+}
+
+// out[e] = table[p * n + e], p = *cur_p (the noise of position p out of a pre-drawn table); p outside 0..npos-1 writes
+// nothing
+__global__ void scan_noise_row_kernel(const float* table, const int* cur_p, int npos, long long n, float* out) {
+    const int p = *cur_p;
+    if (p < 0 || p >= npos) return;
+    const float* src = table + (long long)p * n;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+        out[e] = src[e];
+}
+
+// out[(m K + k) HW + e] = sab[i] x[m HW + e] + omab[i] noise[m HW + e] for k < K, i = *cur_i: perturb_kernel's expression
+// and roundings, each source element read once and stored to the K rows it feeds.  i outside 1..T writes nothing.
+__global__ void scan_perturb_kernel(const float* x, const float* noise, const int* cur_i, const float* sab,
+                                    const float* omab, int M, int K, int HW, int T, float* out) {
+#pragma clang fp contract(off)  // perturb_kernel's separate fp32 roundings (bit-identical to it)
+    const int i = *cur_i;
+    if (i < 1 || i > T) return;
+    const float a = sab[i], b = omab[i];
+    const long long total = (long long)M * HW;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long long)gridDim.x * blockDim.x) {
+        const long long m = q / HW, e = q - m * HW;
+        const float v = a * x[q] + b * noise[q];
+        float* o = out + m * K * HW + e;
+        for (int k = 0; k < K; ++k) o[(long long)k * HW] = v;
+    }
+}
+
+// acc[m ld + k0 + k] += ((double)w[i] * sum_e (double)d (double)d) / HW,  d = pred[(m K + k) HW + e] - noise[m HW + e]
+// formed in fp32, i = *cur_i.  One block per row m K + k; thread t sums elements t, t + 256, ... in order, then a
+// wave64 butterfly and a fixed-order fold of the 4 wave sums through LDS: the same bits in every run, no atomics
+// (a row has one writer).  i outside 1..T writes nothing.
+__global__ __launch_bounds__(256) void scan_mse_accum_kernel(const float* pred, const float* noise, int K, int HW, int T,
+                                                             const int* cur_i, const float* w, double* acc, int ld,
+                                                             int k0) {
+    const int i = *cur_i;
+    if (i < 1 || i > T) return;                         // block-uniform
+    const int row = blockIdx.x, m = row / K, k = row - m * K;
+    const float* pr = pred + (long long)row * HW;
+    const float* nz = noise + (long long)m * HW;
+    double s = 0.0;
+    for (int e = threadIdx.x; e < HW; e += 256) {
+        const float d = pr[e] - nz[e];
+        s = fma((double)d, (double)d, s);               // the product is exact in fp64: fma == multiply, then add
+    }
+    __shared__ double red[4];
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double tot = (red[0] + red[1]) + (red[2] + red[3]);
+        acc[(long long)m * ld + k0 + k] += ((double)w[i] * tot) / (double)HW;
+    }
+}
+
 // per-block partials: [0] sum (pred-noise)^2, [1] sum dpred ; dpred = 2(pred-noise)/numel
 __global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float* noise, long long n, float scale,
                                                   float* dpred, float* partial) {
@@ -1248,11 +1328,6 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, float*
 constexpr int SUMSQ_MAX_BLOCKS = 2048;                   // == CDM_GRAD_SUMSQ_MAX_PARTIALS (cdm_hip.h)
 static inline int grad_sumsq_blocks(long long n) { return nblocks(n, 256 * 16, SUMSQ_MAX_BLOCKS); }
 
-static __device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // partial[blockIdx.x] = sum over this block's elements of (double)g * (double)g.  The base needs 4-byte alignment
 // only: `head` elements up to the first 16-byte boundary and the `n - head` mod 4 after the last float4 go to the
 // first threads of block 0; the float4 body is a grid-stride loop, four loads in flight per thread.
@@ -1667,6 +1742,36 @@ CDM_API int cdm_mse_accum(const float* pred, const float* noise, long long nstri
     if (!t && !cur_i) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mse_accum_kernel, dim3(N), dim3(256), 0, S(stream), pred, noise, nstride, T, HW, t, cur_i, mul,
                        div, acc);
+    return cdm_status();
+}
+CDM_API int cdm_scan_prologue(int* ctr, int npos, int T, const int* pos_t, int* cur_i, int* cur_p, float* t_cur,
+                              const float* sc_table, int sc_row, float* sc_cur, void* stream) {
+    if (!ctr || !pos_t || !cur_i || !cur_p || !t_cur || npos < 1 || T < 1 || (sc_table && (!sc_cur || sc_row < 0)))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_prologue_kernel, dim3(1), dim3(256), 0, S(stream), ctr, npos, T, pos_t, cur_i, cur_p, t_cur,
+                       sc_table, sc_row, sc_cur);
+    return cdm_status();
+}
+CDM_API int cdm_scan_noise_row(const float* table, const int* cur_p, int npos, long long n, float* out, void* stream) {
+    if (!table || !cur_p || !out || npos < 1 || n < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_noise_row_kernel, dim3(nblocks(n)), dim3(256), 0, S(stream), table, cur_p, npos, n, out);
+    return cdm_status();
+}
+CDM_API int cdm_scan_perturb(const float* x0, const float* noise, const int* cur_i, const float* sab, const float* omab,
+                             int M, int K, int HW, int T, float* out, void* stream) {
+    if (!x0 || !noise || !cur_i || !sab || !omab || !out || M < 1 || K < 1 || HW < 1 || T < 1)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_perturb_kernel, dim3(nblocks((long long)M * HW)), dim3(256), 0, S(stream), x0, noise, cur_i,
+                       sab, omab, M, K, HW, T, out);
+    return cdm_status();
+}
+CDM_API int cdm_scan_mse_accum(const float* pred, const float* noise, int M, int K, int HW, const int* cur_i,
+                               const float* w, int T, double* acc, int ld, int k0, void* stream) {
+    if (!pred || !noise || !cur_i || !w || !acc || M < 1 || K < 1 || HW < 1 || T < 1 || k0 < 0 || ld < k0 + K ||
+        (long long)M * K > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_mse_accum_kernel, dim3(M * K), dim3(256), 0, S(stream), pred, noise, K, HW, T, cur_i, w, acc,
+                       ld, k0);
     return cdm_status();
 }
 CDM_API int cdm_mse(const float* pred, const float* noise, long long n, double grad_numel, float* dpred, float* partial,

@@ -1114,6 +1114,13 @@ class DDPM:
         x = a * init.to(dev, torch.float32) + b * torch.as_tensor(noise).to(dev, torch.float32)
         return fn(x, params, guide_w=guide_w, known=known, mask=mask, t_start=t_start, **sampler_kwargs)
 
+    def param_scan(self, maps, candidates, **kwargs):
+        """:func:`cdm_amd.param_scan` of this model under this schedule: ``score[m, k]`` of every map under every
+        candidate parameter vector (lower = preferred) -> ScanResult.  ``kwargs``: t_grid, n_steps, n_noise, weight, seed,
+        noise, max_rows, steps_per_graph."""
+        from .likelihood import param_scan
+        return param_scan(self.model, maps, candidates, self.T, ab_t=self.ab_t, b_t=self.b_t, **kwargs)
+
 
 @torch.no_grad()
 def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.0, timesteps=1000, b_t=None,

@@ -25,6 +25,7 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from ._lib import lib
@@ -282,6 +283,301 @@ def calculate_elbo_and_bpd_dataset(model, dataloader, timesteps, device=None, ab
     given."""
     sched = _sched_tensors(timesteps, ab_t, b_t, a_t)
     return _evaluator(model, timesteps, noise_source, sched).elbo_and_bpd(dataloader)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Parameter scan: which conditioning parameters does the model prefer for a map?  (not in the reference; DESIGN §1)
+# ----------------------------------------------------------------------------------------------------------------------
+SCAN_WEIGHTS = ("uniform", "nll")
+
+
+def param_grid(base, axes) -> torch.Tensor:
+    """The Cartesian grid of candidate parameter vectors [K, ncf] (fp32) over the columns named by ``axes``
+    ({column index: (lo, hi, n)}: n evenly spaced values lo..hi, both ends included), every other column held at
+    ``base`` [ncf].  Rows are ordered with the last axis of ``axes`` (in the dict's order) varying fastest.  Pure host
+    function.  ValueError: a column outside base, n < 1, a spec that is not (lo, hi, n)."""
+    b = np.asarray(torch.as_tensor(base).detach().cpu().numpy() if torch.is_tensor(base) else base,
+                   dtype=np.float64).reshape(-1)
+    cols, lins = [], []
+    for col, spec in dict(axes).items():
+        if isinstance(col, bool) or int(col) != col or not 0 <= int(col) < b.size:
+            raise ValueError(f"axis {col!r} is not a column of the {b.size} parameters")
+        try:
+            lo, hi, n = spec
+        except (TypeError, ValueError):
+            raise ValueError(f"axis {col}: expected (lo, hi, n), got {spec!r}") from None
+        if isinstance(n, bool) or int(n) != n or int(n) < 1:
+            raise ValueError(f"axis {col}: n must be a positive integer, got {n!r}")
+        cols.append(int(col))
+        lins.append(np.linspace(float(lo), float(hi), int(n)))
+    grid = np.tile(b, (int(np.prod([v.size for v in lins], dtype=np.int64)) if lins else 1, 1))
+    if lins:
+        mesh = np.meshgrid(*lins, indexing="ij")
+        for col, v in zip(cols, mesh):
+            grid[:, col] = v.reshape(-1)
+    return torch.from_numpy(grid.astype(np.float32))
+
+
+class ScanResult:
+    """What :func:`param_scan` returns.  ``score`` [M, K] fp64 (on the device the scan ran on; lower is better),
+    ``candidates`` [K, ncf] fp32 (host), ``t_grid`` (list of ints), ``n_noise`` and ``weight`` as the call had them.
+
+    The score is a ranking statistic, not a calibrated log-likelihood (under the reference's (1 - ab) noise factor no
+    weight makes it an ELBO), so the methods that turn it into weights take a ``scale`` the caller must
+    choose — there is no default that would mean something.  Plain tensor code: works on any device, no kernels."""
+
+    def __init__(self, score, candidates, t_grid, n_noise: int = 1, weight: str = "uniform"):
+        self.score = score
+        self.candidates = candidates
+        self.t_grid = [int(t) for t in t_grid]
+        self.n_noise, self.weight = int(n_noise), weight
+
+    def log_weights(self, scale) -> torch.Tensor:
+        """-scale (score - min_k score) [M, K]: 0 at each map's best candidate."""
+        s = self.score
+        return -float(scale) * (s - s.min(dim=1, keepdim=True).values)
+
+    def posterior(self, scale):
+        """(mean [M, ncf], std [M, ncf], weights [M, K]): weights = softmax_k of :meth:`log_weights`, then the weighted
+        mean and standard deviation of the candidates under them (fp64)."""
+        w = torch.softmax(self.log_weights(scale), dim=1)
+        c = self.candidates.to(w.device, w.dtype)
+        mean = w @ c
+        d = c[None] - mean[:, None]
+        std = (w[:, :, None] * d * d).sum(1).sqrt()
+        return mean, std, w
+
+    def best_index(self) -> torch.Tensor:
+        return self.score.argmin(dim=1)
+
+    def best(self) -> torch.Tensor:
+        """The candidate with the lowest score, per map [M, ncf]."""
+        return self.candidates[self.best_index().cpu()]
+
+
+def check_scan(maps, candidates, timesteps, n_cfeat, H, t_grid=None, n_steps=32, n_noise=1, weight="uniform",
+               noise=None, max_rows=256):
+    """Validate and normalise the arguments of a parameter scan, on the host: -> (maps [M, H, H] fp32, candidates
+    [K, ncf] fp32 host, t_grid list, noise [P, M, H, H] fp32 or None).  ValueError, nothing touched: maps not
+    [M, H, H] / [M, 1, H, H]; candidates not [K, n_cfeat]; a t_grid entry outside 1..timesteps or a t_grid that does
+    not increase; n_noise < 1; an unknown weight; M > max_rows; noise not [P, M, H, H] with P = len(t_grid) n_noise."""
+    T = int(timesteps)
+    x = torch.as_tensor(maps).detach()
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 3 or tuple(x.shape[1:]) != (H, H) or x.shape[0] < 1:
+        raise ValueError(f"maps have shape {tuple(torch.as_tensor(maps).shape)}: expected [M, {H}, {H}] or [M, 1, {H}, {H}]")
+    M = x.shape[0]
+    c = torch.as_tensor(candidates).detach()
+    if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != n_cfeat:
+        raise ValueError(f"candidates have shape {tuple(c.shape)}: expected [K, n_cfeat = {n_cfeat}]")
+    if weight not in SCAN_WEIGHTS:
+        raise ValueError(f"weight must be one of {SCAN_WEIGHTS}, got {weight!r}")
+    if isinstance(n_noise, bool) or int(n_noise) != n_noise or int(n_noise) < 1:
+        raise ValueError(f"n_noise must be a positive integer, got {n_noise!r}")
+    if t_grid is None:
+        from .diffusion import timestep_subsequence
+        tg = timestep_subsequence(T, n_steps)
+    else:
+        raw = [v.item() if hasattr(v, "item") else v for v in t_grid]
+        if not raw or any(isinstance(v, bool) or int(v) != v for v in raw):
+            raise ValueError("t_grid must be a non-empty list of integer timesteps")
+        tg = [int(v) for v in raw]
+        if any(t < 1 or t > T for t in tg):
+            raise ValueError(f"t_grid must lie in 1..timesteps = {T}, got {tg}")
+        if any(b <= a for a, b in zip(tg, tg[1:])):
+            raise ValueError("t_grid must be strictly increasing")
+    if int(max_rows) < 1 or M > int(max_rows):
+        raise ValueError(f"{M} maps exceed max_rows = {max_rows}: one forward holds every map at least once")
+    P = len(tg) * int(n_noise)
+    z = None
+    if noise is not None:
+        z = torch.as_tensor(noise).detach()
+        if tuple(z.shape) != (P, M, H, H):
+            raise ValueError(f"noise has shape {tuple(z.shape)}: expected [P = {P}, M = {M}, {H}, {H}]")
+        z = z.to(torch.float32)
+    return x.to(torch.float32), c.to("cpu", torch.float32).contiguous(), tg, z
+
+
+class _ScanRun:
+    """Device state of one chunk shape (M maps x Kc candidates, npos positions): inputs, tables, accumulator, graph."""
+
+    def __init__(self, ps: "ParamScan", M: int, Kc: int, npos: int, table: bool):
+        self.ps, self.M, self.Kc, self.npos = ps, M, Kc, npos
+        m, dev = ps.model, ps.dev
+        H, nf = m.h, m.n_feat
+        E = lambda *sh: torch.empty(*sh, device=dev)
+        I = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        self.HW = H * H
+        self.x0, self.noise = E(M, self.HW), E(M, self.HW)
+        self.xt = E(M * Kc, H, H)
+        self.cbuf = torch.zeros(M * Kc, m.n_cfeat, device=dev)
+        # the captured graph holds this address, so every chunk of this shape accumulates here (ld = Kc, k0 = 0) and
+        # scan() copies the block into the chunk's columns of the score
+        self.acc = torch.zeros(M, Kc, dtype=torch.float64, device=dev)
+        self.t_cur = E(1)
+        self.cur_i, self.cur_p, self.ctr, self.pos_t = I(1), I(1), I(1), I(npos)
+        self.row = 2 * nf
+        self.sc_table, self.sc_cur = E(npos, self.row), E(self.row)
+        self.ztab = E(npos, M * self.HW) if table else None
+        self.ws = ps.eng.workspace(M * Kc, False)
+        self.seed = None
+        self.graph = None
+
+    def step(self, s):
+        ps, lb = self.ps, lib()
+        M, Kc, HW, nf, T = self.M, self.Kc, self.HW, ps.model.n_feat, ps.T
+        lb.cdm_scan_prologue(_p(self.ctr), self.npos, T, _p(self.pos_t), _p(self.cur_i), _p(self.cur_p),
+                             _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+        if self.ztab is None:
+            lb.cdm_philox_normal(_p(self.noise), M * HW, self.seed, 0, _p(self.cur_p), s)     # keyed by (seed, sub = p)
+        else:
+            lb.cdm_scan_noise_row(_p(self.ztab), _p(self.cur_p), self.npos, M * HW, _p(self.noise), s)
+        lb.cdm_scan_perturb(_p(self.x0), _p(self.noise), _p(self.cur_i), _p(ps.sched.sab), _p(ps.sched.omab), M, Kc,
+                            HW, T, _p(self.xt), s)
+        eps = ps.eng.forward(self.ws, ps.P, self.xt, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
+                             M * Kc, s)
+        lb.cdm_scan_mse_accum(_p(eps), _p(self.noise), M, Kc, HW, _p(self.cur_i), _p(ps.w), T, _p(self.acc), Kc, 0, s)
+
+    def load(self, x, c, pos_t, rows, z, seed):
+        dev = self.ps.dev
+        self.x0.copy_(x.to(dev).reshape(self.M, self.HW))
+        self.cbuf.copy_(c.to(dev).repeat(self.M, 1))            # row m Kc + k = candidate k
+        self.pos_t.copy_(pos_t)
+        self.sc_table.copy_(rows)
+        if z is not None:
+            self.ztab.copy_(z.reshape(self.npos, -1))
+        if self.ztab is None and seed != self.seed:
+            self.seed, self.graph = seed, None                   # the captured Philox launch holds the seed
+
+    def run(self):
+        ps = self.ps
+        K = ps.K
+        if ps.use_graph and self.graph is None and self.npos >= K:
+            def warm_up(s):
+                self.ctr.zero_()
+                self.step(s)                                     # every kernel resident
+            self.graph = _capture_steps(warm_up, self.step, K)
+        self.acc.zero_()
+        self.ctr.zero_()
+        done = 0
+        if self.graph is not None:
+            while done + K <= self.npos:
+                self.graph.replay()
+                done += K
+        s = _s()
+        while done < self.npos:
+            self.step(s)
+            done += 1
+
+
+class ParamScan:
+    """Scores maps under candidate conditioning parameters on common noise (the diffusion-classifier statistic).
+
+    For M maps x[m], K candidates c[k] and the P = S R positions p = r S + s (timestep t_p = t_grid[s], repeat r of
+    n_noise = R; S = len(t_grid)), with one standard-normal map z_p[m] and one shortcut row sc_p per position, both shared
+    by all K candidates:
+        x_p[m]     = sab[t_p] x[m] + omab[t_p] z_p[m]                 (perturb_input, its fp32 roundings)
+        eps_p[m,k] = model.eval()(x_p[m], t_p / T, c[k])              (shortcut sc_p)
+        score[m,k] = (1 / R) sum_p w[t_p] mean_pixels (eps_p[m,k] - z_p[m])^2     accumulated in fp64
+    w = 1 ("uniform") or the fp32 rounding of 1 / (2 b_t) ("nll", the weight of calculate_likelihood).  Lower is better.
+    Under the reference's (1 - ab) noise factor no weight makes this an exact ELBO: it is a ranking
+    statistic whose differences across k have low variance because x_p, z_p and sc_p are common.
+
+    Same structure as :class:`LikelihoodEvaluator`: a step is ``cdm_scan_prologue`` (position counter -> timestep, t / T,
+    shortcut row), the noise, ``cdm_scan_perturb``, the eval forward at batch M Kc (row m Kc + k = map m, candidate k)
+    and ``cdm_scan_mse_accum``; ``steps_per_graph`` steps are captured in one hipGraph and replayed, the rest run
+    eagerly.  Candidates go in chunks of Kc = max(1, max_rows // M); every chunk replays all P positions with the same
+    seed and shortcut table, so a candidate's score depends on its chunk only through the forward's arithmetic (h3's
+    per-tensor operand scale is taken over the chunk's batch).
+    Noise: ``noise=None`` draws z_p on the device, ``cdm_philox_normal`` keyed by (seed, sub = p) over the M H W
+    elements — a function of seed, p, m and the pixel alone, whatever K and the chunking; ``noise=`` [P, M, H, H] (host
+    or device) is used as given (the parity mode).
+    Shortcuts: one ``_draw_shortcut_row`` per position, p = 0..P-1 in order, from the CPU RNG, once per call before any
+    chunk runs."""
+
+    def __init__(self, model, timesteps: int, steps_per_graph: int = 8, use_graph: bool = True, sched_tensors=None):
+        self.model, self.T = model, int(timesteps)
+        self.eng, self.P = model._engine_and_params()
+        self.dev = self.P["out.3.weight"].device
+        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
+        self.K = max(1, int(steps_per_graph))
+        self.use_graph = use_graph
+        b = self.sched.b_t.cpu()
+        self._wtab = {"uniform": torch.ones(self.T + 1),
+                      "nll": (1.0 / (2.0 * b.double())).float()}          # evaluated in fp64, rounded once
+        self.w = torch.ones(self.T + 1, device=self.dev)                  # the table the captured kernels read
+        self._runs = {}
+
+    def _run(self, M, Kc, npos, table) -> _ScanRun:
+        key = (M, Kc, npos, table)
+        r = self._runs.get(key)
+        if r is None:
+            r = self._runs[key] = _ScanRun(self, M, Kc, npos, table)
+        return r
+
+    def _refresh(self):
+        eng, P = self.model._engine_and_params()
+        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
+            self.P = P
+            for r in self._runs.values():
+                r.graph = None
+        eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+
+    def scan(self, maps, candidates, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321, noise=None,
+             max_rows=256) -> ScanResult:
+        m = self.model
+        checked = check_scan(maps, candidates, self.T, m.n_cfeat, m.h, t_grid, n_steps, n_noise, weight, noise,
+                             max_rows)
+        return self._scan(*checked, int(n_noise), weight, int(seed), int(max_rows))
+
+    @torch.no_grad()
+    def _scan(self, x, cand, tg, z, R, weight, seed, max_rows) -> ScanResult:
+        M, K, S = x.shape[0], cand.shape[0], len(tg)
+        npos = S * R
+        Kc = min(K, max(1, max_rows // M))
+        pos_t = torch.tensor(tg * R, dtype=torch.int32)                   # position p = r S + s
+        rows = torch.stack([_draw_shortcut_row(self.model.n_feat) for _ in range(npos)])
+        self._refresh()
+        self.w.copy_(self._wtab[weight])
+        score = torch.empty(M, K, dtype=torch.float64, device=self.dev)
+        for k0 in range(0, K, Kc):
+            kc = min(Kc, K - k0)
+            r = self._run(M, kc, npos, z is not None)
+            r.load(x, cand[k0:k0 + kc], pos_t, rows, z, seed)
+            r.run()
+            score[:, k0:k0 + kc] = r.acc / R
+        return ScanResult(score, cand, tg, R, weight)
+
+
+def _scanner(model, timesteps, steps_per_graph=8, sched=None) -> ParamScan:
+    cache = model.__dict__.setdefault("_cdm_param_scan", {})
+    skey = None if sched is None else tuple(v.numpy().tobytes() for v in sched)
+    key = (int(timesteps), int(steps_per_graph), skey)
+    ps = cache.get(key)
+    if ps is None:
+        ps = cache[key] = ParamScan(model, timesteps, steps_per_graph, sched_tensors=sched)
+    return ps
+
+
+def param_scan(model, maps, candidates, timesteps, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321,
+               noise=None, max_rows=256, steps_per_graph=8, ab_t=None, b_t=None) -> ScanResult:
+    """Score every map under every candidate parameter vector: ``score[m, k]``, lower = preferred (:class:`ParamScan` has
+    the definition).  ``maps`` [M, H, H] or [M, 1, H, H]; ``candidates`` [K, n_cfeat] (:func:`param_grid` builds a
+    grid); ``t_grid``: increasing timesteps in 1..timesteps, None = ``timestep_subsequence(timesteps, n_steps)``;
+    ``n_noise``: noise draws per timestep; ``weight``: "uniform" or "nll"; ``noise``: None (device Philox keyed by
+    ``seed``) or a table [P, M, H, H]; ``ab_t`` / ``b_t``: the caller's schedule, as calculate_likelihood takes it.
+    Costs P ceil(K / Kc) forwards of M Kc rows, P = len(t_grid) n_noise, Kc = max(1, max_rows // M).
+
+    The raw score is returned.  Under the reference's non-standard perturbation no weight makes it an exact
+    ELBO: it ranks candidates, and its differences across k are low-variance because the perturbed input, the noise and
+    the shortcut draw are common to all of them.  Arguments are validated before anything touches the device or the
+    CPU RNG (ValueError: :func:`check_scan`)."""
+    sched = _sched_tensors(timesteps, ab_t, b_t, None)
+    checked = check_scan(maps, candidates, timesteps, model.n_cfeat, model.h, t_grid, n_steps, n_noise, weight, noise,
+                         max_rows)
+    return _scanner(model, timesteps, steps_per_graph, sched)._scan(*checked, int(n_noise), weight, int(seed),
+                                                                   int(max_rows))
 
 
 def calculate_elbo_and_bpd(*args, **kwargs):

@@ -55,6 +55,13 @@ Training for guided sampling (all off by default; without them the outputs are t
   --refine-init PATH.npy --refine-t-start T0
                  with --sample-steps: noise the --n-samples maps of the file to the level of the largest sampled
                  timestep <= T0 and denoise from there (late start); writes refined_samples.npy and a "Refinement" line.
+  --scan-maps PATH.npy --scan-candidates PATH.npy [--scan-steps S --scan-noise R --scan-weight uniform|nll]
+                 conditioned runs only: after the sampling above, score every map of the first file (arrays [M,H,W] or
+                 [M,1,H,W], normalised data units) under every parameter vector of the second ([K,NUM_PARAMS], normalised
+                 as the training parameters are) on S of the TIMESTEPS (default min(32, TIMESTEPS)) with R noise draws
+                 each, common to all candidates (cdm_amd.param_scan), and write param_scan.npz: score [M,K] (lower =
+                 preferred), candidates, t_grid, best [M,NUM_PARAMS] (each map's lowest-score candidate); the log gets a
+                 "Parameter scan" line.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -156,7 +163,31 @@ def main(argv=None):
                     help="maps [n,H,W] or [n,1,H,W] (normalised data units) to re-draw from --refine-t-start; n = --n-samples")
     ap.add_argument("--refine-t-start", type=int, default=None, metavar="T0",
                     help="the timestep --refine-init is noised to (the largest sampled timestep <= T0)")
+    ap.add_argument("--scan-maps", default=None, metavar="PATH.npy",
+                    help="maps [M,H,W] or [M,1,H,W] (normalised data units) to score under --scan-candidates")
+    ap.add_argument("--scan-candidates", default=None, metavar="PATH.npy",
+                    help="candidate parameter vectors [K,NUM_PARAMS] (normalised as the training parameters)")
+    ap.add_argument("--scan-steps", type=int, default=None, metavar="S",
+                    help="timesteps the scan visits (default min(32, TIMESTEPS))")
+    ap.add_argument("--scan-noise", type=int, default=1, metavar="R", help="noise draws per scanned timestep")
+    ap.add_argument("--scan-weight", choices=["uniform", "nll"], default="uniform",
+                    help="per-timestep weight of the scan's squared error: 1, or 1 / (2 b_t)")
     a = ap.parse_args(argv)
+    if (a.scan_maps is None) != (a.scan_candidates is None):
+        ap.error("--scan-maps and --scan-candidates go together")
+    a.scan = None
+    if a.scan_maps is not None:
+        if a.num_params is None:
+            ap.error("--scan-maps needs a conditioned run (NUM_PARAMS)")
+        try:
+            from cdm_amd.likelihood import check_scan
+            steps = min(32, a.timesteps) if a.scan_steps is None else a.scan_steps
+            smaps, scand = (np.load(p, allow_pickle=False) for p in (a.scan_maps, a.scan_candidates))
+            x, c, tg, _ = check_scan(smaps, scand, a.timesteps, a.num_params, a.height, None, steps, a.scan_noise,
+                                     a.scan_weight)
+            a.scan = (x, c, tg)
+        except (OSError, ValueError) as e:
+            ap.error(f"--scan-maps / --scan-candidates: {e}")
     if (a.inpaint_known is None) != (a.inpaint_mask is None):
         ap.error("--inpaint-known and --inpaint-mask go together")
     a.inpaint = None
@@ -401,6 +432,16 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
         dt = time.time() - t0
         np.save(os.path.join(out_dir, "refined_samples.npy"), refined.cpu().numpy())
         log.write(f"Refinement of {ns} maps from t_start={a.refine_t_start} (w={a.guide_w}), {how}: {dt:.2f} s\n")
+    if a.scan is not None:
+        smaps, scand, tg = a.scan
+        t0 = time.time()
+        res = d.param_scan(smaps, scand, t_grid=tg, n_noise=a.scan_noise, weight=a.scan_weight)
+        score = res.score.cpu().numpy()
+        dt = time.time() - t0
+        np.savez(os.path.join(out_dir, "param_scan.npz"), score=score, candidates=res.candidates.numpy(),
+                 t_grid=np.asarray(res.t_grid, dtype=np.int64), best=res.best().numpy())
+        log.write(f"Parameter scan of {score.shape[0]} maps under {score.shape[1]} candidates, {len(tg)} timesteps x "
+                  f"{a.scan_noise} noise draws, weight={a.scan_weight}: {dt:.2f} s\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

@@ -385,6 +385,37 @@ int cdm_perturb(const float* x, const float* noise, const int* t, const int* cur
  * acc[n] += (mean (pred - noise)^2 * mul[i]) / div[i], i = t[n] or *cur_i (noise row (T - i)*nstride) */
 int cdm_mse_accum(const float* pred, const float* noise, long long nstride, int T, int N, int HW, const int* t,
                   const int* cur_i, const float* mul, const float* div, float* acc, void* stream);
+/* Parameter scan (likelihood.ParamScan, not in the reference): M maps scored under K candidate contexts each, on the
+ * same perturbed input; the model batch is M K rows, row m K + k = (map m, candidate k).  One step is cdm_scan_prologue,
+ * the noise (cdm_philox_normal with sub_dev = cur_p, or cdm_scan_noise_row), cdm_scan_perturb, the eval forward and
+ * cdm_scan_mse_accum; none of them synchronises, and the step index is read from the device.
+ * cdm_scan_prologue: the step prologue over a position table.  The counter holds the position p = 0..npos-1 and counts
+ * up; pos_t[p] is the timestep of position p, any value of 1..T at any position, so a timestep may repeat and npos may
+ * exceed T (cdm_sample_prologue_sub walks a strictly increasing subsequence with npos <= T and counts down).
+ *   p = *ctr; *ctr = p + 1; *cur_p = p; *cur_i = i = pos_t[p]; *t_cur = (float)((double)i / T); sc_cur = row p of
+ *   sc_table (sc_row floats; sc_table optional).
+ * A counter outside 0..npos-1, or a pos_t[p] outside 1..T, sets *cur_i = 0 and writes nothing else; the scan kernels of
+ * that step then write nothing.  hipErrorInvalidValue, nothing launched: a required pointer null, npos < 1, T < 1,
+ * sc_table without sc_cur. */
+int cdm_scan_prologue(int* ctr, int npos, int T, const int* pos_t, int* cur_i, int* cur_p, float* t_cur,
+                      const float* sc_table, int sc_row, float* sc_cur, void* stream);
+/* out[0..n) = table[*cur_p * n ..]: the noise of the current position out of a pre-drawn table [npos][n].  A *cur_p
+ * outside 0..npos-1 writes nothing.  hipErrorInvalidValue: a pointer null, npos < 1, n < 1. */
+int cdm_scan_noise_row(const float* table, const int* cur_p, int npos, long long n, float* out, void* stream);
+/* out[(m K + k) HW + e] = sab[i] x0[m HW + e] + omab[i] noise[m HW + e] for every k < K, i = *cur_i: x0, noise [M][HW],
+ * out [M K][HW].  The expression and fp32 roundings of cdm_perturb: out is bit-identical to cdm_perturb (cur_i form,
+ * nstride 0) on x0 and noise with every row repeated K times.  Each source element is read once and stored to the K
+ * rows it feeds.  An i outside 1..T writes nothing.  hipErrorInvalidValue, nothing launched: a pointer null; M, K, HW
+ * or T < 1. */
+int cdm_scan_perturb(const float* x0, const float* noise, const int* cur_i, const float* sab, const float* omab, int M,
+                     int K, int HW, int T, float* out, void* stream);
+/* acc[m ld + k0 + k] += ((double)w[i] * sum_e (double)d (double)d) / HW with d = pred[(m K + k) HW + e] - noise[m HW + e]
+ * formed in fp32, i = *cur_i; pred [M K][HW], noise [M][HW], w [T + 1] fp32, acc fp64 [M][ld] (this call owns columns
+ * k0 .. k0 + K - 1).  One block per row; per-thread fp64 sums over a fixed element set, a wave64 butterfly, then a
+ * fixed-order fold of the four wave sums through LDS: two runs give the same bits; no atomics.  An i outside 1..T
+ * writes nothing.  hipErrorInvalidValue, nothing launched: a pointer null; M, K, HW or T < 1; k0 < 0; ld < k0 + K. */
+int cdm_scan_mse_accum(const float* pred, const float* noise, int M, int K, int HW, const int* cur_i, const float* w,
+                       int T, double* acc, int ld, int k0, void* stream);
 /* F.mse_loss + its gradient (code/train_diffusion_condition.py:227): loss = mean over the n elements, dpred =
  * 2 (pred - noise) / grad_numel (grad_numel = n, or the data-parallel count of a ragged global batch);
  * nonfinite (optional): += 1 when the loss is NaN / inf (SURVEY §5 failure guard; read once per epoch) */
