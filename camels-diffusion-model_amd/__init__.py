@@ -10,9 +10,9 @@ from .diffusion import (DDPM, DDIMSampler, DPMSolverSampler, GraphSampler, Progr
                         check_inpaint, ddim_tables, ddim_tables_from_pairs, denoise_add_noise, dpmpp_tables,
                         dpmpp_tables_from_pairs, known_tables, perturb_input, resample_program, sample_ddpm,
                         timestep_subsequence)
-from .likelihood import (LikelihoodEvaluator, ParamScan, ScanResult, calculate_elbo_and_bpd,  # noqa: F401
-                         calculate_elbo_and_bpd_batch, calculate_elbo_and_bpd_dataset, calculate_likelihood,
-                         check_scan, param_grid, param_scan)
+from .likelihood import (FitResult, LikelihoodEvaluator, ParamFit, ParamScan, ScanResult,  # noqa: F401
+                         calculate_elbo_and_bpd, calculate_elbo_and_bpd_batch, calculate_elbo_and_bpd_dataset,
+                         calculate_likelihood, check_fit, check_scan, param_fit, param_grid, param_scan)
 from .model import ContextUnet, EmbedFC, ResidualConvBlock, UnetDown, UnetUp  # noqa: F401
 from .stats import (calculate_power_spectrum_2d, compare_distributions, compare_power_spectra,  # noqa: F401
                     pdfs, power_spectra, power_spectrum)
@@ -27,4 +27,4 @@ __all__ = ["ContextUnet", "EmbedFC", "ResidualConvBlock", "UnetDown", "UnetUp", 
            "calculate_elbo_and_bpd_dataset", "power_spectrum", "power_spectra", "compare_power_spectra",
            "calculate_power_spectrum_2d", "compare_distributions", "pdfs", "augment_maps", "draw_augment_ops",
            "augment_source_index", "check_augment_ops", "param_scan", "param_grid", "ParamScan", "ScanResult",
-           "check_scan"]
+           "check_scan", "param_fit", "ParamFit", "FitResult", "check_fit"]

@@ -1121,6 +1121,13 @@ class DDPM:
         from .likelihood import param_scan
         return param_scan(self.model, maps, candidates, self.T, ab_t=self.ab_t, b_t=self.b_t, **kwargs)
 
+    def param_fit(self, maps, start, **kwargs):
+        """:func:`cdm_amd.param_fit` of this model under this schedule: gradient descent on the scan score from every
+        start -> FitResult.  ``kwargs``: iters, lr, free, bounds, betas, eps, t_grid, n_steps, n_noise, weight, seed,
+        noise, max_rows, steps_per_graph."""
+        from .likelihood import param_fit
+        return param_fit(self.model, maps, start, self.T, ab_t=self.ab_t, b_t=self.b_t, **kwargs)
+
 
 @torch.no_grad()
 def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.0, timesteps=1000, b_t=None,

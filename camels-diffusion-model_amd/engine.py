@@ -717,7 +717,8 @@ class UNetEngine:
     # ------------------------------------------------------------------------------------------
     def backward(self, ws: "Workspace", P, deps: torch.Tensor, G: Dict[str, torch.Tensor], stream: int,
                  out3_bias_done: bool = False, on_stage=None, dx: Optional[torch.Tensor] = None,
-                 dt: Optional[torch.Tensor] = None, dc: Optional[torch.Tensor] = None):
+                 dt: Optional[torch.Tensor] = None, dc: Optional[torch.Tensor] = None,
+                 stop_after: Optional[str] = None):
         """deps [B,H,W] = dL/d eps.  Writes (assigns) every parameter gradient into G[name].
 
         Optional input gradients (the module API under autograd, ContextUnet.py:42-60): dx [B,H,W] = dL/dx (the
@@ -726,7 +727,14 @@ class UNetEngine:
 
         ``on_stage(name)`` is called (on the host, in stream order) as soon as the gradients of a stage
         are final: "out", "up2", "up1", "up0emb", "down2", "down1", "init" — used to start the
-        data-parallel all-reduce of that stage while the rest of the backward runs."""
+        data-parallel all-reduce of that stage while the rest of the backward runs.
+
+        ``stop_after="up0emb"`` returns right after that stage's hook: dt and dc (and the gradients of out, up2, up1, up0
+        and the embeddings) are final there, the down2 / down1 / init backward — which only feeds the encoder's
+        parameter gradients and dx — is not launched, and those entries of G are left unwritten (the parameter fit,
+        likelihood.ParamFit).  None runs everything."""
+        assert stop_after in (None, "up0emb"), stop_after
+        assert stop_after is None or dx is None, "dx is final only after the init stage"
         hook = on_stage or (lambda name: None)
         assert ws.train, "backward needs a train-mode workspace"
         lb = lib(); s = stream
@@ -827,6 +835,8 @@ class UNetEngine:
                 lb.cdm_embed_input_grad(_p(ws.emb_dpre[ma]), _p(P[ma + ".model.0.weight"]), 2 * nf,
                                         _p(ws.emb_dpre[mb]), _p(P[mb + ".model.0.weight"]), nf, rows, in_dim, _p(dv), s)
         hook("up0emb")
+        if stop_after == "up0emb":
+            return
         # ---------------- down2, down1, init ----------------
         for stage in ("down2", "down1"):
             self._stage_bwd(ws, P, stage, G, s)

@@ -354,6 +354,15 @@ class ScanResult:
         """The candidate with the lowest score, per map [M, ncf]."""
         return self.candidates[self.best_index().cpu()]
 
+    def top(self, k: int) -> torch.Tensor:
+        """The k lowest-scoring candidates per map, best first [M, k, ncf] (host fp32) — the natural ``start`` of
+        :func:`param_fit`.  Ties keep the candidates' order.  ValueError: k outside 1..K."""
+        K = self.candidates.shape[0]
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= K:
+            raise ValueError(f"k must be in 1..{K}, got {k!r}")
+        idx = torch.argsort(self.score.cpu(), dim=1, stable=True)[:, :int(k)]
+        return self.candidates[idx]
+
 
 def check_scan(maps, candidates, timesteps, n_cfeat, H, t_grid=None, n_steps=32, n_noise=1, weight="uniform",
                noise=None, max_rows=256):
@@ -578,6 +587,359 @@ def param_scan(model, maps, candidates, timesteps, t_grid=None, n_steps=32, n_no
                          max_rows)
     return _scanner(model, timesteps, steps_per_graph, sched)._scan(*checked, int(n_noise), weight, int(seed),
                                                                    int(max_rows))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Parameter fit: gradient descent on the scan score over the conditioning vector  (not in the reference)
+# ----------------------------------------------------------------------------------------------------------------------
+class FitResult:
+    """What :func:`param_fit` returns (tensors on the device the fit ran on):
+    ``params`` [M, K, ncf] fp32, the parameters with the lowest score each start visited, and ``score`` [M, K] fp64,
+    that score; ``last_params`` [M, K, ncf] after the last update; ``start`` [M, K, ncf] and ``start_score`` [M, K];
+    ``history_score`` / ``history_grad_norm`` [iters + 1, M, K] fp64: the score and the 2-norm of the gradient over the
+    free columns at the parameters of pass n = 1..iters + 1 (the last row is the evaluation after the last update);
+    ``stalled`` [M, K] int32: updates skipped because the score or gradient was not finite; ``t_grid``, ``n_noise``,
+    ``weight`` as the call had them.
+
+    The score is the scan's ranking statistic, not a calibrated log-likelihood: the fit minimises that
+    statistic on one fixed draw of noise and shortcuts.  ``params`` is a point estimate — the spread across starts is
+    not a posterior width and nothing here is an error bar."""
+
+    def __init__(self, params, score, last_params, start, history_score, history_grad_norm, stalled, t_grid,
+                 n_noise: int = 1, weight: str = "uniform"):
+        self.params, self.score, self.last_params, self.start = params, score, last_params, start
+        self.history_score, self.history_grad_norm, self.stalled = history_score, history_grad_norm, stalled
+        self.start_score = history_score[0]
+        self.t_grid = [int(t) for t in t_grid]
+        self.n_noise, self.weight = int(n_noise), weight
+
+    def best_index(self) -> torch.Tensor:
+        return self.score.argmin(dim=1)
+
+    def best(self) -> torch.Tensor:
+        """Per map, the parameters of its lowest-scoring start [M, ncf]."""
+        idx = self.best_index()
+        return self.params[torch.arange(self.params.shape[0], device=idx.device), idx]
+
+
+def check_fit(maps, start, timesteps, n_cfeat, H, iters=50, lr=0.02, free=None, bounds=(0.0, 1.0), betas=(0.9, 0.999),
+              eps=1e-8, t_grid=None, n_steps=32, n_noise=1, weight="uniform", noise=None, max_rows=256, in_channels=1):
+    """Validate and normalise the arguments of a parameter fit, on the host: -> (maps [M, H, H] fp32, start [M, K, ncf]
+    fp32 host, t_grid list, noise [P, M, H, H] fp32 or None, free mask [ncf] int32, lo [ncf] fp64, hi [ncf] fp64).
+    ValueError, nothing touched (neither the device nor the CPU RNG): in_channels > 1; start not [ncf], [K, ncf] or
+    [M, K, ncf]; whatever :func:`check_scan` rejects about maps, t_grid, n_noise, weight, noise and max_rows; iters < 1;
+    lr not finite or not > 0; a beta outside [0, 1); eps not finite or < 0; a free column out of range or listed twice,
+    or no free column; bounds not a pair of scalars or [ncf] vectors, or lo > hi; a start value outside its bounds
+    (it is not clamped)."""
+    if int(in_channels) != 1:
+        raise ValueError("the parameter fit is single-channel, like the samplers and the likelihood (in_channels = 1)")
+    ncf = int(n_cfeat)
+    s = torch.as_tensor(start).detach()
+    if s.dim() not in (1, 2, 3) or s.shape[-1] != ncf or s.numel() == 0:
+        raise ValueError(f"start has shape {tuple(s.shape)}: expected [{ncf}], [K, {ncf}] or [M, K, {ncf}]")
+    x, flat, tg, z = check_scan(maps, s.reshape(-1, ncf), timesteps, ncf, H, t_grid, n_steps, n_noise, weight, noise,
+                                max_rows)
+    M = x.shape[0]
+    if s.dim() == 3 and s.shape[0] != M:
+        raise ValueError(f"start has shape {tuple(s.shape)}: its first axis must be the {M} maps")
+    st = flat.reshape(s.shape) if s.dim() == 3 else flat.reshape(-1, ncf)[None].expand(M, -1, -1)
+    st = st.contiguous()
+    if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
+        raise ValueError(f"iters must be a positive integer, got {iters!r}")
+    if not (math.isfinite(float(lr)) and float(lr) > 0):
+        raise ValueError(f"lr must be finite and > 0, got {lr!r}")
+    try:
+        b1, b2 = (float(b) for b in betas)
+    except (TypeError, ValueError):
+        raise ValueError(f"betas must be a pair, got {betas!r}") from None
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+    if not (math.isfinite(float(eps)) and float(eps) >= 0):
+        raise ValueError(f"eps must be finite and >= 0, got {eps!r}")
+    cols = list(range(ncf)) if free is None else [v.item() if hasattr(v, "item") else v for v in free]
+    if any(isinstance(j, bool) or int(j) != j or not 0 <= int(j) < ncf for j in cols):
+        raise ValueError(f"free columns must lie in 0..{ncf - 1}, got {cols}")
+    cols = [int(j) for j in cols]
+    if len(set(cols)) != len(cols) or not cols:
+        raise ValueError(f"free must name at least one column and none twice, got {cols}")
+    mask = torch.zeros(ncf, dtype=torch.int32)
+    mask[cols] = 1
+    try:
+        lo, hi = bounds
+        lo, hi = (torch.as_tensor(b, dtype=torch.float64).detach().cpu() for b in (lo, hi))
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds must be a pair (lo, hi) of scalars or [{ncf}] vectors") from None
+    if any(b.dim() > 1 or b.numel() not in (1, ncf) for b in (lo, hi)):
+        raise ValueError(f"bounds must be a pair (lo, hi) of scalars or [{ncf}] vectors")
+    lo, hi = (b.reshape(-1).expand(ncf).contiguous() for b in (lo, hi))
+    if not bool((lo <= hi).all()):
+        raise ValueError("bounds: lo must not exceed hi (and neither may be NaN)")
+    s64 = st.double()
+    if not bool(((s64 >= lo) & (s64 <= hi)).all()):
+        raise ValueError("a start value lies outside its bounds (starts are not clamped)")
+    return x, st, tg, z, mask, lo, hi
+
+
+def fit_bias_table(beta1: float, beta2: float, iters: int) -> torch.Tensor:
+    """[iters, 2] fp64: 1 - beta1**n and 1 - beta2**n for n = 1..iters, Python-float expressions evaluated on the host
+    (as trainer.adam_bias_table: no pow on the device)."""
+    return torch.tensor([(1 - beta1 ** float(n), 1 - beta2 ** float(n)) for n in range(1, iters + 1)],
+                        dtype=torch.float64).reshape(iters, 2)
+
+
+class _FitRun:
+    """Device state of one chunk shape (M maps x Kc starts, npos positions, R repeats): the scan run's inputs and
+    tables, the optimiser state, a frozen train-structured workspace and the step graph."""
+
+    def __init__(self, pf: "ParamFit", M: int, Kc: int, npos: int, table: bool, R: int):
+        self.pf, self.M, self.Kc, self.npos, self.R = pf, M, Kc, npos, R
+        m, dev = pf.model, pf.dev
+        H, nf, ncf = m.h, m.n_feat, m.n_cfeat
+        rows = self.rows = M * Kc
+        E = lambda *sh: torch.empty(*sh, device=dev)
+        I = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        D = lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=dev)
+        self.HW = H * H
+        self.x0, self.noise = E(M, self.HW), E(M, self.HW)
+        self.xt, self.deps = E(rows, H, H), E(rows, H, H)
+        self.cbuf = torch.zeros(rows, ncf, device=dev)            # c32: the engine's input, written by cdm_fit_update
+        self.dc = E(rows, ncf)
+        self.c64, self.m, self.v, self.gacc = D(rows, ncf), D(rows, ncf), D(rows, ncf), D(rows, ncf)
+        self.acc = D(M, Kc)                                       # flat index m Kc + k = the batch row
+        self.best_score, self.best_c = D(rows), E(rows, ncf)
+        self.stalled, self.done = I(rows), I(1)
+        self.t_cur = E(1)
+        self.cur_i, self.cur_p, self.ctr, self.pos_t = I(1), I(1), I(1), I(npos)
+        self.row = 2 * nf
+        self.sc_table, self.sc_cur = E(npos, self.row), E(self.row)
+        self.ztab = E(npos, M * self.HW) if table else None
+        self.ws = pf.eng.workspace(rows, True, frozen=True)
+        self.seed = None
+        self.graph = None
+
+    def step(self, s):
+        pf, lb = self.pf, lib()
+        M, Kc, HW, nf, T = self.M, self.Kc, self.HW, pf.model.n_feat, pf.T
+        lb.cdm_scan_prologue(_p(self.ctr), self.npos, T, _p(self.pos_t), _p(self.cur_i), _p(self.cur_p),
+                             _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
+        if self.ztab is None:
+            lb.cdm_philox_normal(_p(self.noise), M * HW, self.seed, 0, _p(self.cur_p), s)     # keyed by (seed, sub = p)
+        else:
+            lb.cdm_scan_noise_row(_p(self.ztab), _p(self.cur_p), self.npos, M * HW, _p(self.noise), s)
+        lb.cdm_scan_perturb(_p(self.x0), _p(self.noise), _p(self.cur_i), _p(pf.sched.sab), _p(pf.sched.omab), M, Kc,
+                            HW, T, _p(self.xt), s)
+        eps = pf.eng.forward(self.ws, pf.P, self.xt, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
+                             self.rows, s, frozen=True)
+        lb.cdm_fit_mse_grad(_p(eps), _p(self.noise), M, Kc, HW, _p(self.cur_i), _p(pf.w), T, 1.0 / self.R, _p(self.acc),
+                            Kc, 0, _p(self.deps), s)
+        pf.eng.backward(self.ws, pf.P, self.deps, pf.G, s, dc=self.dc, stop_after="up0emb")
+        lb.cdm_fit_grad_accum(_p(self.dc), self.rows, self.dc.shape[1], _p(self.gacc), s)
+
+    def load(self, x, c, pos_t, rows, z, seed):
+        dev = self.pf.dev
+        self.x0.copy_(x.to(dev).reshape(self.M, self.HW))
+        self.cbuf.copy_(c.to(dev).reshape(self.rows, -1))       # row m Kc + k = start k of map m
+        self.c64.copy_(self.cbuf)
+        self.best_c.copy_(self.cbuf)
+        self.best_score.fill_(float("inf"))
+        for v in (self.m, self.v, self.gacc, self.acc, self.stalled, self.done, self.ctr):
+            v.zero_()
+        self.pos_t.copy_(pos_t)
+        self.sc_table.copy_(rows)
+        if z is not None:
+            self.ztab.copy_(z.reshape(self.npos, -1))
+        if self.ztab is None and seed != self.seed:
+            self.seed, self.graph = seed, None                   # the captured Philox launch holds the seed
+
+    def positions(self):
+        """One pass: every position once (graph replays, then the eager rest) on the current stream."""
+        pf = self.pf
+        K = pf.K
+        if pf.use_graph and self.graph is None and self.npos >= K:
+            def warm_up(s):
+                self.ctr.zero_()
+                self.step(s)                                     # every kernel resident
+                for v in (self.gacc, self.acc, self.ctr):
+                    v.zero_()
+            self.graph = _capture_steps(warm_up, self.step, K)
+            for v in (self.gacc, self.acc, self.ctr):
+                v.zero_()
+        s = _s()
+        done = 0
+        if self.graph is not None:
+            while done + K <= self.npos:
+                self.graph.replay()
+                done += K
+        while done < self.npos:
+            self.step(s)
+            done += 1
+
+    def run(self, iters, lr, b1, b2, eps, mask, lo, hi, bc, hist_s, hist_g):
+        """iters + 1 passes over the positions, cdm_fit_update after each; the host reads nothing back."""
+        lb, s = lib(), _s()
+        for _ in range(iters + 1):
+            self.positions()
+            lb.cdm_fit_update(_p(self.done), iters, self.rows, self.cbuf.shape[1], _p(self.acc), _p(self.gacc), _p(mask),
+                              _p(lo), _p(hi), lr, b1, b2, eps, _p(bc), _p(self.c64), _p(self.cbuf), _p(self.m),
+                              _p(self.v), _p(self.best_score), _p(self.best_c), _p(hist_s), _p(hist_g),
+                              _p(self.stalled), _p(self.ctr), s)
+
+
+class ParamFit:
+    """Fits the conditioning parameters of maps by gradient descent on the scan score (:class:`ParamScan` has the
+    statistic; DESIGN §1 the definition).
+
+    M maps, K starts per map c0[m, k]; the positions, the noise z_p[m] and the shortcut rows sc_p are the scan's, common
+    to every start and to every iteration, so the objective is a deterministic function of c:
+        eps_p[m,k] = model.eval()(x_p[m], t_p / T, c[m,k])     frozen-BatchNorm train-structured forward, batch M Kc
+        score[m,k] = (1 / R) sum_p w[t_p] mean_pixels (eps_p[m,k] - z_p[m])^2                 fp64
+        deps_p     = fp32(2 w[t_p] / (H W R)) (eps_p - z_p);   g[m,k,:] = sum_p dc_p[m,k,:]   dc_p fp32, the sum fp64
+    and pass n = 1..iters evaluates score and g at the current c, records them, tracks the best, and takes one Adam
+    step in fp64 clamped to the bounds (``cdm_fit_update``); pass iters + 1 evaluates the final c and only records.
+    BatchNorm is frozen on the running statistics and GroupNorm is per sample, so rows do not interact.
+
+    A step is ``cdm_scan_prologue``, the noise, ``cdm_scan_perturb``, the frozen forward, ``cdm_fit_mse_grad``, the
+    engine backward stopped after the embeddings (``stop_after="up0emb"``: dc needs nothing below) and
+    ``cdm_fit_grad_accum``; ``steps_per_graph`` steps are captured in one hipGraph and replayed, the rest and the
+    update run eagerly; nothing is read back between iterations.  Starts go in chunks of Kc = max(1, max_rows // M):
+    independent fits on the same positions, seed and shortcut rows (under h3 a row's arithmetic depends on its chunk
+    through the per-tensor operand scale).  Cost: (iters + 1) P ceil(K / Kc) forward + backward pairs of M Kc rows.
+    Shortcuts: one ``_draw_shortcut_row`` per position from the CPU RNG, once per call before any chunk runs — a fit
+    and a scan after the same torch.manual_seed see the same objective.
+
+    The fit runs on the engine's train pack (``repack(P, True)``, as a module call under autograd does): the pack token
+    is renewed and the model's eval pack invalidated, so a Trainer, a pending autograd backward or an eval call sharing
+    the engine afterwards repacks its own weights."""
+
+    def __init__(self, model, timesteps: int, steps_per_graph: int = 8, use_graph: bool = True, sched_tensors=None):
+        self.model, self.T = model, int(timesteps)
+        self.eng, self.P = model._engine_and_params()
+        self.dev = self.P["out.3.weight"].device
+        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
+        self.K = max(1, int(steps_per_graph))
+        self.use_graph = use_graph
+        b = self.sched.b_t.cpu()
+        self._wtab = {"uniform": torch.ones(self.T + 1),
+                      "nll": (1.0 / (2.0 * b.double())).float()}          # the scan's tables
+        self.w = torch.ones(self.T + 1, device=self.dev)
+        # scratch parameter gradients of the truncated backward (written, never read)
+        self.G = {n: torch.empty_like(self.P[n]) for n in model._param_names}
+        self._runs = {}
+
+    def _run(self, M, Kc, npos, table, R) -> _FitRun:
+        key = (M, Kc, npos, table, R)
+        r = self._runs.get(key)
+        if r is None:
+            r = self._runs[key] = _FitRun(self, M, Kc, npos, table, R)
+        return r
+
+    def _refresh(self):
+        eng, P = self.model._engine_and_params()
+        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
+            self.P = P
+            self.G = {n: torch.empty_like(P[n]) for n in self.model._param_names}
+            for r in self._runs.values():
+                r.graph = None
+        eng.repack(self.P, True, _s())
+        eng.train_pack_token = object()
+        self.model._invalidate_eval_pack()
+
+    def fit(self, maps, start, iters=50, lr=0.02, free=None, bounds=(0.0, 1.0), betas=(0.9, 0.999), eps=1e-8,
+            t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321, noise=None, max_rows=256) -> FitResult:
+        m = self.model
+        checked = check_fit(maps, start, self.T, m.n_cfeat, m.h, iters, lr, free, bounds, betas, eps, t_grid, n_steps,
+                            n_noise, weight, noise, max_rows, m.in_channels)
+        return self._fit(*checked, int(iters), float(lr), tuple(float(b) for b in betas), float(eps), int(n_noise),
+                         weight, int(seed), int(max_rows))
+
+    @torch.no_grad()
+    def value_and_grad(self, maps, c, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321, noise=None,
+                       max_rows=256):
+        """One evaluation of the objective at ``c`` ([ncf], [K, ncf] or [M, K, ncf]; no bounds apply): -> (score [M, K]
+        fp64, g [M, K, ncf] fp64 = d score / d c), the quantities pass 1 of :meth:`fit` hands to the update.  Draws the
+        shortcut rows as a fit does."""
+        m = self.model
+        big = float("inf")
+        x, st, tg, z, _, _, _ = check_fit(maps, c, self.T, m.n_cfeat, m.h, 1, 1.0, None, (-big, big), (0.0, 0.0), 0.0,
+                                          t_grid, n_steps, n_noise, weight, noise, max_rows, m.in_channels)
+        M, K, ncf = st.shape
+        score = torch.empty(M, K, dtype=torch.float64, device=self.dev)
+        g = torch.empty(M, K, ncf, dtype=torch.float64, device=self.dev)
+        for sl, r in self._chunks(x, st, tg, z, int(n_noise), weight, int(seed), int(max_rows)):
+            r.positions()
+            score[:, sl] = r.acc
+            g[:, sl] = r.gacc.view(M, -1, ncf)
+        return score, g
+
+    def _chunks(self, x, start, tg, z, R, weight, seed, max_rows):
+        """The chunk loop shared by :meth:`_fit` and :meth:`value_and_grad`: draws the shortcut rows (once, before any
+        chunk runs), refreshes the pack and the weight table, then yields (columns k0 .. k0 + kc of the starts, the
+        loaded run) for every chunk of Kc = max(1, max_rows // M) starts."""
+        M, K, _ = start.shape
+        npos = len(tg) * R
+        Kc = min(K, max(1, max_rows // M))
+        pos_t = torch.tensor(tg * R, dtype=torch.int32)                   # position p = r S + s
+        rows = torch.stack([_draw_shortcut_row(self.model.n_feat) for _ in range(npos)])
+        self._refresh()
+        self.w.copy_(self._wtab[weight])
+        for k0 in range(0, K, Kc):
+            kc = min(Kc, K - k0)
+            r = self._run(M, kc, npos, z is not None, R)
+            r.load(x, start[:, k0:k0 + kc], pos_t, rows, z, seed)
+            yield slice(k0, k0 + kc), r
+
+    @torch.no_grad()
+    def _fit(self, x, start, tg, z, mask, lo, hi, iters, lr, betas, eps, R, weight, seed, max_rows) -> FitResult:
+        M, K, ncf = start.shape
+        dev = self.dev
+        mask, lo, hi = mask.to(dev), lo.to(dev), hi.to(dev)
+        bc = fit_bias_table(betas[0], betas[1], iters).to(dev)
+        D = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
+        score, hist_s, hist_g = D(M, K), D(iters + 1, M, K), D(iters + 1, M, K)
+        params, last = torch.empty(M, K, ncf, device=dev), torch.empty(M, K, ncf, device=dev)
+        stalled = torch.empty(M, K, dtype=torch.int32, device=dev)
+        for sl, r in self._chunks(x, start, tg, z, R, weight, seed, max_rows):
+            kc = r.Kc
+            hs, hg = D(iters + 1, M * kc), D(iters + 1, M * kc)
+            r.run(iters, lr, betas[0], betas[1], eps, mask, lo, hi, bc, hs, hg)
+            score[:, sl] = r.best_score.view(M, kc)
+            params[:, sl] = r.best_c.view(M, kc, ncf)
+            last[:, sl] = r.cbuf.view(M, kc, ncf)
+            stalled[:, sl] = r.stalled.view(M, kc)
+            hist_s[:, :, sl] = hs.view(iters + 1, M, kc)
+            hist_g[:, :, sl] = hg.view(iters + 1, M, kc)
+        return FitResult(params, score, last, start.to(dev), hist_s, hist_g, stalled, tg, R, weight)
+
+
+def _fitter(model, timesteps, steps_per_graph=8, sched=None) -> ParamFit:
+    cache = model.__dict__.setdefault("_cdm_param_fit", {})
+    skey = None if sched is None else tuple(v.numpy().tobytes() for v in sched)
+    key = (int(timesteps), int(steps_per_graph), skey)
+    pf = cache.get(key)
+    if pf is None:
+        pf = cache[key] = ParamFit(model, timesteps, steps_per_graph, sched_tensors=sched)
+    return pf
+
+
+def param_fit(model, maps, start, timesteps, iters=50, lr=0.02, free=None, bounds=(0.0, 1.0), betas=(0.9, 0.999),
+              eps=1e-8, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321, noise=None, max_rows=256,
+              steps_per_graph=8, ab_t=None, b_t=None) -> FitResult:
+    """Descend the scan score of every map from every start: ``iters`` Adam steps in fp64 on the conditioning vector,
+    clamped to ``bounds`` (:class:`ParamFit` has the definition, :class:`FitResult` the output).  ``maps`` [M, H, H] or
+    [M, 1, H, H]; ``start`` [ncf], [K, ncf] (shared by all maps) or [M, K, ncf] — ``ScanResult.top(k)`` is the natural
+    one; ``free``: the columns to fit (None = all; the others keep their bits); ``bounds``: (lo, hi), scalars or [ncf]
+    vectors; ``t_grid``, ``n_steps``, ``n_noise``, ``weight``, ``seed``, ``noise``, ``max_rows``, ``ab_t`` / ``b_t`` as
+    :func:`param_scan` takes them.  Costs (iters + 1) P ceil(K / Kc) forward + backward pairs of M Kc rows.
+
+    The score is a ranking statistic, not a calibrated likelihood: the result is the minimiser of that
+    statistic on one fixed draw of noise, a point estimate with no error bar.  Arguments are validated before anything
+    touches the device or the CPU RNG (ValueError: :func:`check_fit`)."""
+    sched = _sched_tensors(timesteps, ab_t, b_t, None)
+    checked = check_fit(maps, start, timesteps, model.n_cfeat, model.h, iters, lr, free, bounds, betas, eps, t_grid,
+                        n_steps, n_noise, weight, noise, max_rows, model.in_channels)
+    return _fitter(model, timesteps, steps_per_graph, sched)._fit(
+        *checked, int(iters), float(lr), tuple(float(b) for b in betas), float(eps), int(n_noise), weight, int(seed),
+        int(max_rows))
 
 
 def calculate_elbo_and_bpd(*args, **kwargs):

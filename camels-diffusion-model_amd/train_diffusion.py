@@ -62,6 +62,15 @@ Training for guided sampling (all off by default; without them the outputs are t
                  each, common to all candidates (cdm_amd.param_scan), and write param_scan.npz: score [M,K] (lower =
                  preferred), candidates, t_grid, best [M,NUM_PARAMS] (each map's lowest-score candidate); the log gets a
                  "Parameter scan" line.
+  --fit-maps PATH.npy (--fit-start PATH.npy | --fit-from-scan K) [--fit-iters N --fit-lr LR --fit-free 0,1,...
+                 --fit-steps S --fit-noise R --fit-weight uniform|nll]
+                 conditioned runs only: descend the scan score of every map of the first file over the conditioning
+                 parameters (cdm_amd.param_fit; Adam in fp64, clamped to [0, 1]) from the starts of the second file
+                 ([NUM_PARAMS], [K,NUM_PARAMS] or [M,K,NUM_PARAMS]) or from each map's K lowest-scoring candidates of the
+                 --scan-* run (which must then score the same maps); --fit-free lists the columns to fit (default all).
+                 Writes param_fit.npz: params and score (the best each start visited), start, last_params,
+                 history_score and history_grad_norm [N+1,M,K], t_grid, best [M,NUM_PARAMS]; the log gets a
+                 "Parameter fit" line.  The score is a ranking statistic: the result is a point estimate, not a posterior.
   --resume PATH  write trainer_epoch_N.pt (parameters, BatchNorm buffers, Adam moments, EMA, step and RNG counters,
                  epoch and loss logs) beside every model checkpoint; if PATH names such a file, continue from it at
                  the epoch after the one it was written in, with that epoch's learning rate.
@@ -172,6 +181,20 @@ def main(argv=None):
     ap.add_argument("--scan-noise", type=int, default=1, metavar="R", help="noise draws per scanned timestep")
     ap.add_argument("--scan-weight", choices=["uniform", "nll"], default="uniform",
                     help="per-timestep weight of the scan's squared error: 1, or 1 / (2 b_t)")
+    ap.add_argument("--fit-maps", default=None, metavar="PATH.npy",
+                    help="maps [M,H,W] or [M,1,H,W] (normalised data units) whose parameters are fitted")
+    ap.add_argument("--fit-start", default=None, metavar="PATH.npy",
+                    help="starts [NUM_PARAMS], [K,NUM_PARAMS] or [M,K,NUM_PARAMS] (normalised as the training parameters)")
+    ap.add_argument("--fit-from-scan", type=int, default=None, metavar="K",
+                    help="start from each map's K lowest-scoring --scan-candidates (needs --scan-maps = the fitted maps)")
+    ap.add_argument("--fit-iters", type=int, default=50, metavar="N", help="Adam steps of the fit")
+    ap.add_argument("--fit-lr", type=float, default=0.02, metavar="LR", help="step size of the fit")
+    ap.add_argument("--fit-free", default=None, metavar="0,1,...", help="columns to fit (default: all)")
+    ap.add_argument("--fit-steps", type=int, default=None, metavar="S",
+                    help="timesteps the fit visits (default min(32, TIMESTEPS))")
+    ap.add_argument("--fit-noise", type=int, default=1, metavar="R", help="noise draws per fitted timestep")
+    ap.add_argument("--fit-weight", choices=["uniform", "nll"], default="uniform",
+                    help="per-timestep weight of the fit's squared error: 1, or 1 / (2 b_t)")
     a = ap.parse_args(argv)
     if (a.scan_maps is None) != (a.scan_candidates is None):
         ap.error("--scan-maps and --scan-candidates go together")
@@ -188,6 +211,37 @@ def main(argv=None):
             a.scan = (x, c, tg)
         except (OSError, ValueError) as e:
             ap.error(f"--scan-maps / --scan-candidates: {e}")
+    a.fit = None
+    if a.fit_maps is None and (a.fit_start is not None or a.fit_from_scan is not None):
+        ap.error("--fit-start / --fit-from-scan need --fit-maps")
+    if a.fit_maps is not None:
+        if a.num_params is None:
+            ap.error("--fit-maps needs a conditioned run (NUM_PARAMS)")
+        if (a.fit_start is None) == (a.fit_from_scan is None):
+            ap.error("--fit-maps needs exactly one of --fit-start and --fit-from-scan")
+        if a.fit_from_scan is not None and a.scan is None:
+            ap.error("--fit-from-scan needs --scan-maps and --scan-candidates")
+        try:
+            from cdm_amd.likelihood import check_fit
+            free = None if a.fit_free is None else [int(v) for v in a.fit_free.split(",")]
+            steps = min(32, a.timesteps) if a.fit_steps is None else a.fit_steps
+            fmaps = np.load(a.fit_maps, allow_pickle=False)
+            if a.fit_from_scan is not None:
+                K = a.fit_from_scan
+                if not 1 <= K <= a.scan[1].shape[0]:
+                    raise ValueError(f"--fit-from-scan {K}: the scan has {a.scan[1].shape[0]} candidates")
+                if tuple(np.squeeze(fmaps).shape) != tuple(np.squeeze(a.scan[0].numpy()).shape) or \
+                        not np.array_equal(np.squeeze(fmaps).astype(np.float32), np.squeeze(a.scan[0].numpy())):
+                    raise ValueError("--fit-from-scan: --fit-maps and --scan-maps must hold the same maps")
+                fstart = a.scan[1][:K]                 # stands in for the scan's top K while the arguments are checked
+            else:
+                fstart = np.load(a.fit_start, allow_pickle=False)
+            x, st, tg, _, _, _, _ = check_fit(fmaps, fstart, a.timesteps, a.num_params, a.height, a.fit_iters, a.fit_lr,
+                                              free, (0.0, 1.0), (0.9, 0.999), 1e-8, None, steps, a.fit_noise,
+                                              a.fit_weight)
+            a.fit = (x, None if a.fit_from_scan is not None else st, tg, free)
+        except (OSError, ValueError) as e:
+            ap.error(f"--fit-maps / --fit-start / --fit-from-scan: {e}")
     if (a.inpaint_known is None) != (a.inpaint_mask is None):
         ap.error("--inpaint-known and --inpaint-mask go together")
     a.inpaint = None
@@ -442,6 +496,21 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
                  t_grid=np.asarray(res.t_grid, dtype=np.int64), best=res.best().numpy())
         log.write(f"Parameter scan of {score.shape[0]} maps under {score.shape[1]} candidates, {len(tg)} timesteps x "
                   f"{a.scan_noise} noise draws, weight={a.scan_weight}: {dt:.2f} s\n")
+    if a.fit is not None:
+        fmaps, fstart, ftg, free = a.fit
+        if fstart is None:
+            fstart = res.top(a.fit_from_scan)           # [M, K, NUM_PARAMS]: each map's K lowest-scoring candidates
+        t0 = time.time()
+        fr = d.param_fit(fmaps, fstart, iters=a.fit_iters, lr=a.fit_lr, free=free, t_grid=ftg, n_noise=a.fit_noise,
+                         weight=a.fit_weight)
+        fscore = fr.score.cpu().numpy()
+        dt = time.time() - t0
+        np.savez(os.path.join(out_dir, "param_fit.npz"), params=fr.params.cpu().numpy(), score=fscore,
+                 start=fr.start.cpu().numpy(), last_params=fr.last_params.cpu().numpy(),
+                 history_score=fr.history_score.cpu().numpy(), history_grad_norm=fr.history_grad_norm.cpu().numpy(),
+                 t_grid=np.asarray(fr.t_grid, dtype=np.int64), best=fr.best().cpu().numpy())
+        log.write(f"Parameter fit of {fscore.shape[0]} maps from {fscore.shape[1]} starts, {a.fit_iters} iterations, "
+                  f"{len(ftg)} timesteps x {a.fit_noise} noise draws, weight={a.fit_weight}: {dt:.2f} s\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

@@ -416,6 +416,42 @@ int cdm_scan_perturb(const float* x0, const float* noise, const int* cur_i, cons
  * writes nothing.  hipErrorInvalidValue, nothing launched: a pointer null; M, K, HW or T < 1; k0 < 0; ld < k0 + K. */
 int cdm_scan_mse_accum(const float* pred, const float* noise, int M, int K, int HW, const int* cur_i, const float* w,
                        int T, double* acc, int ld, int k0, void* stream);
+/* Parameter fit (likelihood.ParamFit, not in the reference; csrc/fit.hip): gradient descent on the scan score over the
+ * conditioning vector.  A step is cdm_scan_prologue, the noise, cdm_scan_perturb, the frozen train-structured forward,
+ * cdm_fit_mse_grad, the engine backward up to the embeddings (dc) and cdm_fit_grad_accum; cdm_fit_update closes a pass
+ * over all positions.  None of them synchronises or allocates.
+ * cdm_fit_mse_grad: cdm_scan_mse_accum's term with the 1 / R folded in, and the objective's gradient at the network
+ * output in the same pass:
+ *   d = pred[(m K + k) HW + e] - noise[m HW + e]                         fp32
+ *   acc[m ld + k0 + k] += (((double)w[i] * sum_e (double)d (double)d) / HW) * inv_R
+ *   deps[(m K + k) HW + e] = coef * d,  coef = (float)(((2.0 * (double)w[i]) * inv_R) / HW)    one fp32 product
+ * i = *cur_i; an i outside 1..T writes nothing (acc and deps keep their bits).  Any HW >= 1: float4 loads / stores on
+ * the 16-byte aligned body of a row, scalar head and tail.  One block per row, per-thread fp64 sums over a fixed
+ * element set, a wave64 butterfly, a fixed-order fold: two runs give the same bits; no atomics.
+ * hipErrorInvalidValue, nothing launched: a pointer null; M, K, HW or T < 1; k0 < 0; ld < k0 + K; inv_R <= 0. */
+int cdm_fit_mse_grad(const float* pred, const float* noise, int M, int K, int HW, const int* cur_i, const float* w,
+                     int T, double inv_R, double* acc, int ld, int k0, float* deps, void* stream);
+/* gacc[q] += (double)dc[q] for q < rows ncf (dc fp32 [rows][ncf] from the engine backward, gacc fp64).
+ * hipErrorInvalidValue: a pointer null, rows or ncf < 1. */
+int cdm_fit_grad_accum(const float* dc, int rows, int ncf, double* gacc, void* stream);
+/* One pass of the fit closes here.  *done (device int) = passes completed; this is pass n = *done + 1 of iters + 1.
+ * Per row r (score[r] = the accumulated objective, g = gacc[r][:]), all in fp64 with contraction off:
+ *   gnorm = sqrt(sum over free columns j ascending of g[j] g[j]);  finite = isfinite(score) and every free g[j] finite
+ *   hist_score[(n - 1) rows + r] = score;  hist_gnorm[(n - 1) rows + r] = gnorm
+ *   score < best_score[r]:  best_score[r] = score, best_c[r][:] = c32[r][:] (the parameters the score was taken at)
+ *   n <= iters and finite, per free column j (bc1 = bc[2 (n - 1)], bc2 = bc[2 (n - 1) + 1], the host-built
+ *   1 - beta1^n and 1 - beta2^n):
+ *     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g)
+ *     c64 = clamp(c64 - (lr (m / bc1)) / (sqrt(v / bc2) + eps), lo[j], hi[j]);  c32 = (float)c64
+ *   n <= iters and not finite:  stalled[r] += 1, the row's c64, c32, m, v keep their bits
+ *   a column with free_mask[j] == 0 keeps its bits always; pass n = iters + 1 records and tracks the best only.
+ * Then score and gacc are cleared, *pos_ctr (optional: the scan prologue's position counter) is reset to 0 and *done
+ * becomes n.  *done outside 0..iters: nothing is read or written.  One block (a pass is rows ncf elements).
+ * hipErrorInvalidValue, nothing launched: a required pointer null; iters, rows or ncf < 1. */
+int cdm_fit_update(int* done, int iters, int rows, int ncf, double* score, double* gacc, const int* free_mask,
+                   const double* lo, const double* hi, double lr, double beta1, double beta2, double eps, const double* bc,
+                   double* c64, float* c32, double* m, double* v, double* best_score, float* best_c, double* hist_score,
+                   double* hist_gnorm, int* stalled, int* pos_ctr, void* stream);
 /* F.mse_loss + its gradient (code/train_diffusion_condition.py:227): loss = mean over the n elements, dpred =
  * 2 (pred - noise) / grad_numel (grad_numel = n, or the data-parallel count of a ragged global batch);
  * nonfinite (optional): += 1 when the loss is NaN / inf (SURVEY §5 failure guard; read once per epoch) */
