@@ -85,6 +85,26 @@ def _capture_steps(warm_up, step, K: int):
     return g
 
 
+def _run_steps(graph, step, K: int, total: int):
+    """``total`` steps on the current stream: replays of ``graph`` (K captured steps; None = no graph) while a whole one
+    fits, then ``step(stream)`` eagerly for the rest."""
+    done = 0
+    if graph is not None:
+        while done + K <= total:
+            graph.replay()
+            done += K
+    s = _s()
+    for _ in range(done, total):
+        step(s)
+
+
+def _rehomed(model, P):
+    """The model's current parameter dict if any tensor of ``P`` changed address (a captured graph and a weight pack hold
+    the old ones), else None."""
+    new = model._engine_and_params()[1]
+    return new if any(new[k].data_ptr() != v.data_ptr() for k, v in P.items()) else None
+
+
 def sqrt_scalar_f32(v: torch.Tensor) -> torch.Tensor:
     """fp32 sqrt of every element as a 0-d tensor op computes it: IEEE correctly rounded, the same on every host
     (round(sqrt_fp64(x)) equals the correctly rounded fp32 sqrt: 53 >= 2 * 24 + 2 bits)."""
@@ -712,10 +732,10 @@ class GraphSampler:
 
     def prepare(self):
         """Refresh the eval weight pack and capture the step graph (idempotent)."""
-        eng, P = self.model._engine_and_params()
-        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
+        P = _rehomed(self.model, self.P)
+        if P is not None:
             self.P, self.graph = P, None                    # parameters were re-homed: re-capture
-        eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+        self.eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
         if self.use_graph and self.graph is None and self.npos >= self.K:
             self.graph = _capture_steps(self._warm_up, self._step, self.K)
 
@@ -742,15 +762,7 @@ class GraphSampler:
         if self.cfg:
             self.xbuf[n:] = self.xbuf[:n]
         self.ctr.fill_(self.npos)
-        done = 0
-        if self.graph is not None:
-            while done + self.K <= total:
-                self.graph.replay()
-                done += self.K
-        s = _s()
-        while done < total:
-            self._step(s)
-            done += 1
+        _run_steps(self.graph, self._step, self.K, total)
         x = self.xbuf[:n].reshape(n, 1, H, H).clone()
         inter = None
         if self.nslots:

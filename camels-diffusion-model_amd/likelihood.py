@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
-from .diffusion import Schedule, _capture_steps, _draw_shortcut_row, _p, _s
+from .diffusion import Schedule, _capture_steps, _draw_shortcut_row, _p, _rehomed, _run_steps, _s
 
 
 def _split_batch(item):
@@ -38,6 +38,52 @@ def _split_batch(item):
     x = item[0]
     c = item[1] if len(item) > 1 else None
     return x, c
+
+
+def _pos_int(name, v, lo=1, hi=None, msg=None) -> int:
+    """int(v) of an integral, non-bool ``v`` in lo..hi (hi None: no upper end); ValueError(``msg``, or "<name> must be
+    a positive integer, got <v>") otherwise."""
+    if isinstance(v, bool) or int(v) != v or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError(msg or f"{name} must be a positive integer, got {v!r}")
+    return int(v)
+
+
+class _ModelDriver:
+    """What the evaluator, the scan and the fit share: the model's engine and parameters, the schedule, the steps per
+    graph, and one run object (device buffers + step graph) per key, built as ``run_type(self, *key)``."""
+    run_type = None
+
+    def __init__(self, model, timesteps: int, steps_per_graph: int, use_graph: bool, sched_tensors):
+        self.model, self.T = model, int(timesteps)
+        self.eng, self.P = model._engine_and_params()
+        self.dev = self.P["out.3.weight"].device
+        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
+        self.K = max(1, int(steps_per_graph))
+        self.use_graph = use_graph
+        self._runs = {}
+
+    def _run(self, *key):
+        r = self._runs.get(key)
+        if r is None:
+            r = self._runs[key] = self.run_type(self, *key)
+        return r
+
+    def _rehome(self, P):
+        """The parameters moved to the tensors ``P``: every captured graph holds the old addresses."""
+        self.P = P
+        for r in self._runs.values():
+            r.graph = None
+
+    def _repack(self):
+        self.eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+
+    def _refresh(self):
+        """Refresh the weight pack (the eval pack, unless a subclass says otherwise); drop graphs if the parameters were
+        re-homed."""
+        P = _rehomed(self.model, self.P)
+        if P is not None:
+            self._rehome(P)
+        self._repack()
 
 
 class _EvalRun:
@@ -109,22 +155,18 @@ class _EvalRun:
         self.acc.zero_()
 
 
-class LikelihoodEvaluator:
+class LikelihoodEvaluator(_ModelDriver):
     """Holds the schedule tables, the per-batch-size runs and graphs of one model."""
+    run_type = _EvalRun
 
     def __init__(self, model, timesteps: int, noise_source: str = "device", steps_per_graph: int = 10,
                  seed: int = 4321, use_graph: bool = True, sched_tensors=None):
         """``sched_tensors=(b_t, a_t, ab_t)``: the caller's schedule (the reference functions take them as
         arguments and use them as given); None builds the default schedule of the training scripts."""
         assert noise_source in ("device", "host")
-        self.model, self.T = model, int(timesteps)
-        self.eng, self.P = model._engine_and_params()
-        self.dev = self.P["out.3.weight"].device
-        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
+        super().__init__(model, timesteps, steps_per_graph, use_graph, sched_tensors)
         self.noise_source = noise_source
         self.seed = seed
-        self.K = max(1, int(steps_per_graph))
-        self.use_graph = use_graph
         self.rng_ctr = torch.zeros(1, dtype=torch.int32, device=self.dev)
         b, _, ab = (v.cpu() for v in self.sched.tensors())
         # reference fp32 expressions, evaluated once into per-step tables
@@ -133,23 +175,6 @@ class LikelihoodEvaluator:
         self.elbo_mul = (0.5 * (b / (1.0 - ab))).to(self.dev)                # paper.py:122
         self.elbo_div = torch.full((self.T + 1,), 10.0, device=self.dev)     # paper.py:124
         self.sqrt_omab = torch.sqrt(1 - ab).to(self.dev)                     # paper.py:112
-        self._runs = {}
-
-    # ------------------------------------------------------------------------------------------
-    def _run(self, B: int) -> _EvalRun:
-        r = self._runs.get(B)
-        if r is None:
-            r = self._runs[B] = _EvalRun(self, B)
-        return r
-
-    def _refresh(self):
-        """Refresh the eval pack; drop graphs if the parameters were re-homed."""
-        eng, P = self.model._engine_and_params()
-        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
-            self.P = P
-            for r in self._runs.values():
-                r.graph = None
-        eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -174,15 +199,7 @@ class LikelihoodEvaluator:
             r.capture(self.K)
             r.acc.zero_()
         r.ctr.fill_(T)
-        done = 0
-        if r.graph is not None:
-            while done + self.K <= T:
-                r.graph.replay()
-                done += self.K
-        s = _s()
-        while done < T:
-            r.step(s, self.nll_mul, self.nll_div, self.sched.omab)
-            done += 1
+        _run_steps(r.graph, lambda s: r.step(s, self.nll_mul, self.nll_div, self.sched.omab), self.K, T)
         return r.acc
 
     @torch.no_grad()
@@ -242,14 +259,21 @@ def _sched_tensors(timesteps, ab_t, b_t, a_t):
     return b[:n].contiguous(), a[:n].contiguous(), ab[:n].contiguous()
 
 
-def _evaluator(model, timesteps, noise_source="device", sched=None) -> LikelihoodEvaluator:
-    cache = model.__dict__.setdefault("_cdm_lik_eval", {})
-    skey = None if sched is None else tuple(v.numpy().tobytes() for v in sched)
-    key = (int(timesteps), noise_source, skey)
-    ev = cache.get(key)
-    if ev is None:
-        ev = cache[key] = LikelihoodEvaluator(model, timesteps, noise_source, sched_tensors=sched)
-    return ev
+def _cached(model, slot: str, key, build):
+    """The driver ``build()`` of one ``key`` = (timesteps, noise source or steps per graph, schedule tensors or None),
+    kept in the dict ``model.<slot>`` so that its graphs outlive the call."""
+    cache = model.__dict__.setdefault(slot, {})
+    T, opt, sched = key
+    key = (int(T), opt, None if sched is None else tuple(v.numpy().tobytes() for v in sched))
+    drv = cache.get(key)
+    if drv is None:
+        drv = cache[key] = build()
+    return drv
+
+
+def _evaluator(model, timesteps, noise_source, sched) -> LikelihoodEvaluator:
+    return _cached(model, "_cdm_lik_eval", (timesteps, noise_source, sched),
+                   lambda: LikelihoodEvaluator(model, timesteps, noise_source, sched_tensors=sched))
 
 
 def calculate_likelihood(model, dataloader, timesteps, device=None, ab_t=None, b_t=None, a_t=None,
@@ -300,16 +324,12 @@ def param_grid(base, axes) -> torch.Tensor:
                    dtype=np.float64).reshape(-1)
     cols, lins = [], []
     for col, spec in dict(axes).items():
-        if isinstance(col, bool) or int(col) != col or not 0 <= int(col) < b.size:
-            raise ValueError(f"axis {col!r} is not a column of the {b.size} parameters")
+        cols.append(_pos_int("axis", col, 0, b.size - 1, f"axis {col!r} is not a column of the {b.size} parameters"))
         try:
             lo, hi, n = spec
         except (TypeError, ValueError):
             raise ValueError(f"axis {col}: expected (lo, hi, n), got {spec!r}") from None
-        if isinstance(n, bool) or int(n) != n or int(n) < 1:
-            raise ValueError(f"axis {col}: n must be a positive integer, got {n!r}")
-        cols.append(int(col))
-        lins.append(np.linspace(float(lo), float(hi), int(n)))
+        lins.append(np.linspace(float(lo), float(hi), _pos_int(f"axis {col}: n", n)))
     grid = np.tile(b, (int(np.prod([v.size for v in lins], dtype=np.int64)) if lins else 1, 1))
     if lins:
         mesh = np.meshgrid(*lins, indexing="ij")
@@ -318,7 +338,19 @@ def param_grid(base, axes) -> torch.Tensor:
     return torch.from_numpy(grid.astype(np.float32))
 
 
-class ScanResult:
+class _Result:
+    """What a scan's and a fit's result share: ``score`` [M, K] fp64 (lower is better) and the call's positions."""
+
+    def __init__(self, score, t_grid, n_noise: int, weight: str):
+        self.score = score
+        self.t_grid = [int(t) for t in t_grid]
+        self.n_noise, self.weight = int(n_noise), weight
+
+    def best_index(self) -> torch.Tensor:
+        return self.score.argmin(dim=1)
+
+
+class ScanResult(_Result):
     """What :func:`param_scan` returns.  ``score`` [M, K] fp64 (on the device the scan ran on; lower is better),
     ``candidates`` [K, ncf] fp32 (host), ``t_grid`` (list of ints), ``n_noise`` and ``weight`` as the call had them.
 
@@ -327,10 +359,8 @@ class ScanResult:
     choose — there is no default that would mean something.  Plain tensor code: works on any device, no kernels."""
 
     def __init__(self, score, candidates, t_grid, n_noise: int = 1, weight: str = "uniform"):
-        self.score = score
+        super().__init__(score, t_grid, n_noise, weight)
         self.candidates = candidates
-        self.t_grid = [int(t) for t in t_grid]
-        self.n_noise, self.weight = int(n_noise), weight
 
     def log_weights(self, scale) -> torch.Tensor:
         """-scale (score - min_k score) [M, K]: 0 at each map's best candidate."""
@@ -347,9 +377,6 @@ class ScanResult:
         std = (w[:, :, None] * d * d).sum(1).sqrt()
         return mean, std, w
 
-    def best_index(self) -> torch.Tensor:
-        return self.score.argmin(dim=1)
-
     def best(self) -> torch.Tensor:
         """The candidate with the lowest score, per map [M, ncf]."""
         return self.candidates[self.best_index().cpu()]
@@ -358,9 +385,8 @@ class ScanResult:
         """The k lowest-scoring candidates per map, best first [M, k, ncf] (host fp32) — the natural ``start`` of
         :func:`param_fit`.  Ties keep the candidates' order.  ValueError: k outside 1..K."""
         K = self.candidates.shape[0]
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= K:
-            raise ValueError(f"k must be in 1..{K}, got {k!r}")
-        idx = torch.argsort(self.score.cpu(), dim=1, stable=True)[:, :int(k)]
+        k = _pos_int("k", k, 1, K, f"k must be in 1..{K}, got {k!r}")
+        idx = torch.argsort(self.score.cpu(), dim=1, stable=True)[:, :k]
         return self.candidates[idx]
 
 
@@ -382,8 +408,7 @@ def check_scan(maps, candidates, timesteps, n_cfeat, H, t_grid=None, n_steps=32,
         raise ValueError(f"candidates have shape {tuple(c.shape)}: expected [K, n_cfeat = {n_cfeat}]")
     if weight not in SCAN_WEIGHTS:
         raise ValueError(f"weight must be one of {SCAN_WEIGHTS}, got {weight!r}")
-    if isinstance(n_noise, bool) or int(n_noise) != n_noise or int(n_noise) < 1:
-        raise ValueError(f"n_noise must be a positive integer, got {n_noise!r}")
+    _pos_int("n_noise", n_noise)
     if t_grid is None:
         from .diffusion import timestep_subsequence
         tg = timestep_subsequence(T, n_steps)
@@ -408,50 +433,54 @@ def check_scan(maps, candidates, timesteps, n_cfeat, H, t_grid=None, n_steps=32,
     return x.to(torch.float32), c.to("cpu", torch.float32).contiguous(), tg, z
 
 
-class _ScanRun:
-    """Device state of one chunk shape (M maps x Kc candidates, npos positions): inputs, tables, accumulator, graph."""
+class _PositionRun:
+    """Device state of one chunk shape (M maps x Kc rows per map, npos positions) and the walk over the positions that
+    the scan and the fit share: inputs, noise, tables, the fp64 score accumulator, the step graph.  A subclass supplies
+    ``_workspace()``, ``_score(s)`` (what follows the perturbation in a step), ``_cleared()`` and its own state."""
 
-    def __init__(self, ps: "ParamScan", M: int, Kc: int, npos: int, table: bool):
-        self.ps, self.M, self.Kc, self.npos = ps, M, Kc, npos
-        m, dev = ps.model, ps.dev
-        H, nf = m.h, m.n_feat
+    def __init__(self, drv: "_PositionDriver", M: int, Kc: int, npos: int, table: bool):
+        self.drv, self.M, self.Kc, self.npos = drv, M, Kc, npos
+        m, dev = drv.model, drv.dev
+        H, rows = m.h, M * Kc
         E = lambda *sh: torch.empty(*sh, device=dev)
         I = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
-        self.HW = H * H
+        self.HW, self.rows = H * H, rows
         self.x0, self.noise = E(M, self.HW), E(M, self.HW)
-        self.xt = E(M * Kc, H, H)
-        self.cbuf = torch.zeros(M * Kc, m.n_cfeat, device=dev)
-        # the captured graph holds this address, so every chunk of this shape accumulates here (ld = Kc, k0 = 0) and
-        # scan() copies the block into the chunk's columns of the score
+        self.xt = E(rows, H, H)
+        self.cbuf = torch.zeros(rows, m.n_cfeat, device=dev)
+        # the captured graph holds this address, so every chunk of this shape accumulates here (ld = Kc, k0 = 0; flat
+        # index m Kc + k = the batch row) and the driver copies the block into the chunk's columns of the score
         self.acc = torch.zeros(M, Kc, dtype=torch.float64, device=dev)
         self.t_cur = E(1)
         self.cur_i, self.cur_p, self.ctr, self.pos_t = I(1), I(1), I(1), I(npos)
-        self.row = 2 * nf
+        self.row = 2 * m.n_feat
         self.sc_table, self.sc_cur = E(npos, self.row), E(self.row)
         self.ztab = E(npos, M * self.HW) if table else None
-        self.ws = ps.eng.workspace(M * Kc, False)
+        self.ws = self._workspace()
         self.seed = None
         self.graph = None
 
-    def step(self, s):
-        ps, lb = self.ps, lib()
-        M, Kc, HW, nf, T = self.M, self.Kc, self.HW, ps.model.n_feat, ps.T
+    def _perturbed(self, s):
+        """Position ctr -> its timestep, t / T and shortcut row; its noise; x_p into ``xt``, each map Kc times."""
+        d, lb = self.drv, lib()
+        M, HW, T = self.M, self.HW, d.T
         lb.cdm_scan_prologue(_p(self.ctr), self.npos, T, _p(self.pos_t), _p(self.cur_i), _p(self.cur_p),
                              _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
         if self.ztab is None:
             lb.cdm_philox_normal(_p(self.noise), M * HW, self.seed, 0, _p(self.cur_p), s)     # keyed by (seed, sub = p)
         else:
             lb.cdm_scan_noise_row(_p(self.ztab), _p(self.cur_p), self.npos, M * HW, _p(self.noise), s)
-        lb.cdm_scan_perturb(_p(self.x0), _p(self.noise), _p(self.cur_i), _p(ps.sched.sab), _p(ps.sched.omab), M, Kc,
+        lb.cdm_scan_perturb(_p(self.x0), _p(self.noise), _p(self.cur_i), _p(d.sched.sab), _p(d.sched.omab), M, self.Kc,
                             HW, T, _p(self.xt), s)
-        eps = ps.eng.forward(self.ws, ps.P, self.xt, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
-                             M * Kc, s)
-        lb.cdm_scan_mse_accum(_p(eps), _p(self.noise), M, Kc, HW, _p(self.cur_i), _p(ps.w), T, _p(self.acc), Kc, 0, s)
+
+    def step(self, s):
+        self._perturbed(s)
+        self._score(s)
 
     def load(self, x, c, pos_t, rows, z, seed):
-        dev = self.ps.dev
-        self.x0.copy_(x.to(dev).reshape(self.M, self.HW))
-        self.cbuf.copy_(c.to(dev).repeat(self.M, 1))            # row m Kc + k = candidate k
+        """``c`` [M Kc, ncf]: the context of every batch row."""
+        self.x0.copy_(x.to(self.drv.dev).reshape(self.M, self.HW))
+        self.cbuf.copy_(c)
         self.pos_t.copy_(pos_t)
         self.sc_table.copy_(rows)
         if z is not None:
@@ -459,28 +488,84 @@ class _ScanRun:
         if self.ztab is None and seed != self.seed:
             self.seed, self.graph = seed, None                   # the captured Philox launch holds the seed
 
-    def run(self):
-        ps = self.ps
-        K = ps.K
-        if ps.use_graph and self.graph is None and self.npos >= K:
+    def positions(self):
+        """One pass: every position once (graph replays, then the eager rest) on the current stream, adding into the
+        accumulators as they stand.  What holds here, for both subclasses:
+
+        * The graph is captured on first use.  The capture's warm-up launch is one real step: it advances ``ctr`` and
+          adds into the accumulators, so ``_cleared()`` (every accumulator of the subclass) and ``ctr`` are zeroed
+          after it, and the pass that triggered the capture starts exactly as one that found the graph ready.
+        * A pass that does not capture launches its steps and nothing else.  The fit relies on it: between its passes
+          ``cdm_fit_update`` clears ``acc``, ``gacc`` and ``ctr`` on the device and the host clears nothing.  The scan
+          clears ``acc`` and ``ctr`` itself before every pass (:meth:`_ScanRun.run`).
+        * In device-noise mode a changed seed has dropped the graph (:meth:`load`); a table-noise run never looks at
+          the seed."""
+        K = self.drv.K
+        if self.drv.use_graph and self.graph is None and self.npos >= K:
             def warm_up(s):
                 self.ctr.zero_()
                 self.step(s)                                     # every kernel resident
             self.graph = _capture_steps(warm_up, self.step, K)
+            for v in (*self._cleared(), self.ctr):
+                v.zero_()
+        _run_steps(self.graph, self.step, K, self.npos)
+
+
+class _ScanRun(_PositionRun):
+    """The scan's run: eval workspace; a step ends with the eval forward and ``cdm_scan_mse_accum``."""
+
+    def _workspace(self):
+        return self.drv.eng.workspace(self.rows, False)
+
+    def _score(self, s):
+        d, nf = self.drv, self.drv.model.n_feat
+        eps = d.eng.forward(self.ws, d.P, self.xt, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
+                            self.rows, s)
+        lib().cdm_scan_mse_accum(_p(eps), _p(self.noise), self.M, self.Kc, self.HW, _p(self.cur_i), _p(d.w), d.T,
+                                 _p(self.acc), self.Kc, 0, s)
+
+    def _cleared(self):
+        return (self.acc,)
+
+    def load(self, x, c, *walk):
+        super().load(x, c.to(self.drv.dev).repeat(self.M, 1), *walk)        # row m Kc + k = candidate k
+
+    def run(self):
         self.acc.zero_()
         self.ctr.zero_()
-        done = 0
-        if self.graph is not None:
-            while done + K <= self.npos:
-                self.graph.replay()
-                done += K
-        s = _s()
-        while done < self.npos:
-            self.step(s)
-            done += 1
+        self.positions()
 
 
-class ParamScan:
+class _PositionDriver(_ModelDriver):
+    """What the scan and the fit share beyond :class:`_ModelDriver`: the weight tables and the chunk loop."""
+
+    def __init__(self, model, timesteps: int, steps_per_graph: int = 8, use_graph: bool = True, sched_tensors=None):
+        super().__init__(model, timesteps, steps_per_graph, use_graph, sched_tensors)
+        b = self.sched.b_t.cpu()
+        self._wtab = {"uniform": torch.ones(self.T + 1),
+                      "nll": (1.0 / (2.0 * b.double())).float()}          # evaluated in fp64, rounded once
+        self.w = torch.ones(self.T + 1, device=self.dev)                  # the table the captured kernels read
+
+    def _chunks(self, x, c, tg, z, R, weight, seed, max_rows, *extra):
+        """The chunk loop of a scan, a fit and :meth:`ParamFit.value_and_grad` over the K = c.shape[-2] candidates or
+        starts ``c`` ([K, ncf] or [M, K, ncf]): draws the shortcut rows (once, before any chunk runs), refreshes the
+        pack and the weight table, then yields (columns k0 .. k0 + kc, the loaded run) for every chunk of
+        Kc = max(1, max_rows // M).  ``extra``: what keys a run beyond its shape and noise mode."""
+        M, K = x.shape[0], c.shape[-2]
+        npos = len(tg) * R
+        Kc = min(K, max(1, max_rows // M))
+        pos_t = torch.tensor(tg * R, dtype=torch.int32)                   # position p = r S + s
+        rows = torch.stack([_draw_shortcut_row(self.model.n_feat) for _ in range(npos)])
+        self._refresh()
+        self.w.copy_(self._wtab[weight])
+        for k0 in range(0, K, Kc):
+            kc = min(Kc, K - k0)
+            r = self._run(M, kc, npos, z is not None, *extra)
+            r.load(x, c[..., k0:k0 + kc, :], pos_t, rows, z, seed)
+            yield slice(k0, k0 + kc), r
+
+
+class ParamScan(_PositionDriver):
     """Scores maps under candidate conditioning parameters on common noise (the diffusion-classifier statistic).
 
     For M maps x[m], K candidates c[k] and the P = S R positions p = r S + s (timestep t_p = t_grid[s], repeat r of
@@ -505,33 +590,7 @@ class ParamScan:
     Shortcuts: one ``_draw_shortcut_row`` per position, p = 0..P-1 in order, from the CPU RNG, once per call before any
     chunk runs."""
 
-    def __init__(self, model, timesteps: int, steps_per_graph: int = 8, use_graph: bool = True, sched_tensors=None):
-        self.model, self.T = model, int(timesteps)
-        self.eng, self.P = model._engine_and_params()
-        self.dev = self.P["out.3.weight"].device
-        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
-        self.K = max(1, int(steps_per_graph))
-        self.use_graph = use_graph
-        b = self.sched.b_t.cpu()
-        self._wtab = {"uniform": torch.ones(self.T + 1),
-                      "nll": (1.0 / (2.0 * b.double())).float()}          # evaluated in fp64, rounded once
-        self.w = torch.ones(self.T + 1, device=self.dev)                  # the table the captured kernels read
-        self._runs = {}
-
-    def _run(self, M, Kc, npos, table) -> _ScanRun:
-        key = (M, Kc, npos, table)
-        r = self._runs.get(key)
-        if r is None:
-            r = self._runs[key] = _ScanRun(self, M, Kc, npos, table)
-        return r
-
-    def _refresh(self):
-        eng, P = self.model._engine_and_params()
-        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
-            self.P = P
-            for r in self._runs.values():
-                r.graph = None
-        eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+    run_type = _ScanRun
 
     def scan(self, maps, candidates, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321, noise=None,
              max_rows=256) -> ScanResult:
@@ -542,31 +601,11 @@ class ParamScan:
 
     @torch.no_grad()
     def _scan(self, x, cand, tg, z, R, weight, seed, max_rows) -> ScanResult:
-        M, K, S = x.shape[0], cand.shape[0], len(tg)
-        npos = S * R
-        Kc = min(K, max(1, max_rows // M))
-        pos_t = torch.tensor(tg * R, dtype=torch.int32)                   # position p = r S + s
-        rows = torch.stack([_draw_shortcut_row(self.model.n_feat) for _ in range(npos)])
-        self._refresh()
-        self.w.copy_(self._wtab[weight])
-        score = torch.empty(M, K, dtype=torch.float64, device=self.dev)
-        for k0 in range(0, K, Kc):
-            kc = min(Kc, K - k0)
-            r = self._run(M, kc, npos, z is not None)
-            r.load(x, cand[k0:k0 + kc], pos_t, rows, z, seed)
+        score = torch.empty(x.shape[0], cand.shape[0], dtype=torch.float64, device=self.dev)
+        for sl, r in self._chunks(x, cand, tg, z, R, weight, seed, max_rows):
             r.run()
-            score[:, k0:k0 + kc] = r.acc / R
+            score[:, sl] = r.acc / R
         return ScanResult(score, cand, tg, R, weight)
-
-
-def _scanner(model, timesteps, steps_per_graph=8, sched=None) -> ParamScan:
-    cache = model.__dict__.setdefault("_cdm_param_scan", {})
-    skey = None if sched is None else tuple(v.numpy().tobytes() for v in sched)
-    key = (int(timesteps), int(steps_per_graph), skey)
-    ps = cache.get(key)
-    if ps is None:
-        ps = cache[key] = ParamScan(model, timesteps, steps_per_graph, sched_tensors=sched)
-    return ps
 
 
 def param_scan(model, maps, candidates, timesteps, t_grid=None, n_steps=32, n_noise=1, weight="uniform", seed=4321,
@@ -585,14 +624,15 @@ def param_scan(model, maps, candidates, timesteps, t_grid=None, n_steps=32, n_no
     sched = _sched_tensors(timesteps, ab_t, b_t, None)
     checked = check_scan(maps, candidates, timesteps, model.n_cfeat, model.h, t_grid, n_steps, n_noise, weight, noise,
                          max_rows)
-    return _scanner(model, timesteps, steps_per_graph, sched)._scan(*checked, int(n_noise), weight, int(seed),
-                                                                   int(max_rows))
+    ps = _cached(model, "_cdm_param_scan", (timesteps, int(steps_per_graph), sched),
+                 lambda: ParamScan(model, timesteps, steps_per_graph, sched_tensors=sched))
+    return ps._scan(*checked, int(n_noise), weight, int(seed), int(max_rows))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # Parameter fit: gradient descent on the scan score over the conditioning vector  (not in the reference)
 # ----------------------------------------------------------------------------------------------------------------------
-class FitResult:
+class FitResult(_Result):
     """What :func:`param_fit` returns (tensors on the device the fit ran on):
     ``params`` [M, K, ncf] fp32, the parameters with the lowest score each start visited, and ``score`` [M, K] fp64,
     that score; ``last_params`` [M, K, ncf] after the last update; ``start`` [M, K, ncf] and ``start_score`` [M, K];
@@ -607,14 +647,10 @@ class FitResult:
 
     def __init__(self, params, score, last_params, start, history_score, history_grad_norm, stalled, t_grid,
                  n_noise: int = 1, weight: str = "uniform"):
-        self.params, self.score, self.last_params, self.start = params, score, last_params, start
+        super().__init__(score, t_grid, n_noise, weight)
+        self.params, self.last_params, self.start = params, last_params, start
         self.history_score, self.history_grad_norm, self.stalled = history_score, history_grad_norm, stalled
         self.start_score = history_score[0]
-        self.t_grid = [int(t) for t in t_grid]
-        self.n_noise, self.weight = int(n_noise), weight
-
-    def best_index(self) -> torch.Tensor:
-        return self.score.argmin(dim=1)
 
     def best(self) -> torch.Tensor:
         """Per map, the parameters of its lowest-scoring start [M, ncf]."""
@@ -644,8 +680,7 @@ def check_fit(maps, start, timesteps, n_cfeat, H, iters=50, lr=0.02, free=None, 
         raise ValueError(f"start has shape {tuple(s.shape)}: its first axis must be the {M} maps")
     st = flat.reshape(s.shape) if s.dim() == 3 else flat.reshape(-1, ncf)[None].expand(M, -1, -1)
     st = st.contiguous()
-    if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
-        raise ValueError(f"iters must be a positive integer, got {iters!r}")
+    _pos_int("iters", iters)
     if not (math.isfinite(float(lr)) and float(lr) > 0):
         raise ValueError(f"lr must be finite and > 0, got {lr!r}")
     try:
@@ -657,9 +692,7 @@ def check_fit(maps, start, timesteps, n_cfeat, H, iters=50, lr=0.02, free=None, 
     if not (math.isfinite(float(eps)) and float(eps) >= 0):
         raise ValueError(f"eps must be finite and >= 0, got {eps!r}")
     cols = list(range(ncf)) if free is None else [v.item() if hasattr(v, "item") else v for v in free]
-    if any(isinstance(j, bool) or int(j) != j or not 0 <= int(j) < ncf for j in cols):
-        raise ValueError(f"free columns must lie in 0..{ncf - 1}, got {cols}")
-    cols = [int(j) for j in cols]
+    cols = [_pos_int("free", j, 0, ncf - 1, f"free columns must lie in 0..{ncf - 1}, got {cols}") for j in cols]
     if len(set(cols)) != len(cols) or not cols:
         raise ValueError(f"free must name at least one column and none twice, got {cols}")
     mask = torch.zeros(ncf, dtype=torch.int32)
@@ -687,92 +720,45 @@ def fit_bias_table(beta1: float, beta2: float, iters: int) -> torch.Tensor:
                         dtype=torch.float64).reshape(iters, 2)
 
 
-class _FitRun:
-    """Device state of one chunk shape (M maps x Kc starts, npos positions, R repeats): the scan run's inputs and
-    tables, the optimiser state, a frozen train-structured workspace and the step graph."""
+class _FitRun(_PositionRun):
+    """The fit's run (R repeats per timestep): the optimiser state and a frozen train-structured workspace; a step ends
+    with the frozen forward, ``cdm_fit_mse_grad``, the truncated backward and ``cdm_fit_grad_accum``.  ``cbuf`` is c32,
+    the engine's input, written by ``cdm_fit_update``."""
 
     def __init__(self, pf: "ParamFit", M: int, Kc: int, npos: int, table: bool, R: int):
-        self.pf, self.M, self.Kc, self.npos, self.R = pf, M, Kc, npos, R
-        m, dev = pf.model, pf.dev
-        H, nf, ncf = m.h, m.n_feat, m.n_cfeat
-        rows = self.rows = M * Kc
-        E = lambda *sh: torch.empty(*sh, device=dev)
-        I = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
-        D = lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=dev)
-        self.HW = H * H
-        self.x0, self.noise = E(M, self.HW), E(M, self.HW)
-        self.xt, self.deps = E(rows, H, H), E(rows, H, H)
-        self.cbuf = torch.zeros(rows, ncf, device=dev)            # c32: the engine's input, written by cdm_fit_update
-        self.dc = E(rows, ncf)
+        super().__init__(pf, M, Kc, npos, table)
+        self.R = R
+        rows, ncf = self.cbuf.shape
+        E = lambda *sh: torch.empty(*sh, device=pf.dev)
+        I = lambda n: torch.zeros(n, dtype=torch.int32, device=pf.dev)
+        D = lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=pf.dev)
+        self.deps, self.dc = E(*self.xt.shape), E(rows, ncf)
         self.c64, self.m, self.v, self.gacc = D(rows, ncf), D(rows, ncf), D(rows, ncf), D(rows, ncf)
-        self.acc = D(M, Kc)                                       # flat index m Kc + k = the batch row
         self.best_score, self.best_c = D(rows), E(rows, ncf)
         self.stalled, self.done = I(rows), I(1)
-        self.t_cur = E(1)
-        self.cur_i, self.cur_p, self.ctr, self.pos_t = I(1), I(1), I(1), I(npos)
-        self.row = 2 * nf
-        self.sc_table, self.sc_cur = E(npos, self.row), E(self.row)
-        self.ztab = E(npos, M * self.HW) if table else None
-        self.ws = pf.eng.workspace(rows, True, frozen=True)
-        self.seed = None
-        self.graph = None
 
-    def step(self, s):
-        pf, lb = self.pf, lib()
-        M, Kc, HW, nf, T = self.M, self.Kc, self.HW, pf.model.n_feat, pf.T
-        lb.cdm_scan_prologue(_p(self.ctr), self.npos, T, _p(self.pos_t), _p(self.cur_i), _p(self.cur_p),
-                             _p(self.t_cur), _p(self.sc_table), self.row, _p(self.sc_cur), s)
-        if self.ztab is None:
-            lb.cdm_philox_normal(_p(self.noise), M * HW, self.seed, 0, _p(self.cur_p), s)     # keyed by (seed, sub = p)
-        else:
-            lb.cdm_scan_noise_row(_p(self.ztab), _p(self.cur_p), self.npos, M * HW, _p(self.noise), s)
-        lb.cdm_scan_perturb(_p(self.x0), _p(self.noise), _p(self.cur_i), _p(pf.sched.sab), _p(pf.sched.omab), M, Kc,
-                            HW, T, _p(self.xt), s)
+    def _workspace(self):
+        return self.drv.eng.workspace(self.rows, True, frozen=True)
+
+    def _score(self, s):
+        pf, lb, nf = self.drv, lib(), self.drv.model.n_feat
         eps = pf.eng.forward(self.ws, pf.P, self.xt, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
                              self.rows, s, frozen=True)
-        lb.cdm_fit_mse_grad(_p(eps), _p(self.noise), M, Kc, HW, _p(self.cur_i), _p(pf.w), T, 1.0 / self.R, _p(self.acc),
-                            Kc, 0, _p(self.deps), s)
+        lb.cdm_fit_mse_grad(_p(eps), _p(self.noise), self.M, self.Kc, self.HW, _p(self.cur_i), _p(pf.w), pf.T,
+                            1.0 / self.R, _p(self.acc), self.Kc, 0, _p(self.deps), s)
         pf.eng.backward(self.ws, pf.P, self.deps, pf.G, s, dc=self.dc, stop_after="up0emb")
         lb.cdm_fit_grad_accum(_p(self.dc), self.rows, self.dc.shape[1], _p(self.gacc), s)
 
-    def load(self, x, c, pos_t, rows, z, seed):
-        dev = self.pf.dev
-        self.x0.copy_(x.to(dev).reshape(self.M, self.HW))
-        self.cbuf.copy_(c.to(dev).reshape(self.rows, -1))       # row m Kc + k = start k of map m
+    def _cleared(self):
+        return self.acc, self.gacc
+
+    def load(self, x, c, *walk):
+        super().load(x, c.to(self.drv.dev).reshape(self.rows, -1), *walk)     # row m Kc + k = start k of map m
         self.c64.copy_(self.cbuf)
         self.best_c.copy_(self.cbuf)
         self.best_score.fill_(float("inf"))
         for v in (self.m, self.v, self.gacc, self.acc, self.stalled, self.done, self.ctr):
             v.zero_()
-        self.pos_t.copy_(pos_t)
-        self.sc_table.copy_(rows)
-        if z is not None:
-            self.ztab.copy_(z.reshape(self.npos, -1))
-        if self.ztab is None and seed != self.seed:
-            self.seed, self.graph = seed, None                   # the captured Philox launch holds the seed
-
-    def positions(self):
-        """One pass: every position once (graph replays, then the eager rest) on the current stream."""
-        pf = self.pf
-        K = pf.K
-        if pf.use_graph and self.graph is None and self.npos >= K:
-            def warm_up(s):
-                self.ctr.zero_()
-                self.step(s)                                     # every kernel resident
-                for v in (self.gacc, self.acc, self.ctr):
-                    v.zero_()
-            self.graph = _capture_steps(warm_up, self.step, K)
-            for v in (self.gacc, self.acc, self.ctr):
-                v.zero_()
-        s = _s()
-        done = 0
-        if self.graph is not None:
-            while done + K <= self.npos:
-                self.graph.replay()
-                done += K
-        while done < self.npos:
-            self.step(s)
-            done += 1
 
     def run(self, iters, lr, b1, b2, eps, mask, lo, hi, bc, hist_s, hist_g):
         """iters + 1 passes over the positions, cdm_fit_update after each; the host reads nothing back."""
@@ -785,7 +771,7 @@ class _FitRun:
                               _p(self.stalled), _p(self.ctr), s)
 
 
-class ParamFit:
+class ParamFit(_PositionDriver):
     """Fits the conditioning parameters of maps by gradient descent on the scan score (:class:`ParamScan` has the
     statistic; DESIGN §1 the definition).
 
@@ -811,37 +797,20 @@ class ParamFit:
     is renewed and the model's eval pack invalidated, so a Trainer, a pending autograd backward or an eval call sharing
     the engine afterwards repacks its own weights."""
 
+    run_type = _FitRun
+
     def __init__(self, model, timesteps: int, steps_per_graph: int = 8, use_graph: bool = True, sched_tensors=None):
-        self.model, self.T = model, int(timesteps)
-        self.eng, self.P = model._engine_and_params()
-        self.dev = self.P["out.3.weight"].device
-        self.sched = Schedule(self.T, self.dev, tensors=sched_tensors)
-        self.K = max(1, int(steps_per_graph))
-        self.use_graph = use_graph
-        b = self.sched.b_t.cpu()
-        self._wtab = {"uniform": torch.ones(self.T + 1),
-                      "nll": (1.0 / (2.0 * b.double())).float()}          # the scan's tables
-        self.w = torch.ones(self.T + 1, device=self.dev)
+        super().__init__(model, timesteps, steps_per_graph, use_graph, sched_tensors)
+        self._rehome(self.P)
+
+    def _rehome(self, P):
+        super()._rehome(P)
         # scratch parameter gradients of the truncated backward (written, never read)
-        self.G = {n: torch.empty_like(self.P[n]) for n in model._param_names}
-        self._runs = {}
+        self.G = {n: torch.empty_like(P[n]) for n in self.model._param_names}
 
-    def _run(self, M, Kc, npos, table, R) -> _FitRun:
-        key = (M, Kc, npos, table, R)
-        r = self._runs.get(key)
-        if r is None:
-            r = self._runs[key] = _FitRun(self, M, Kc, npos, table, R)
-        return r
-
-    def _refresh(self):
-        eng, P = self.model._engine_and_params()
-        if any(P[k].data_ptr() != v.data_ptr() for k, v in self.P.items()):
-            self.P = P
-            self.G = {n: torch.empty_like(P[n]) for n in self.model._param_names}
-            for r in self._runs.values():
-                r.graph = None
-        eng.repack(self.P, True, _s())
-        eng.train_pack_token = object()
+    def _repack(self):
+        self.eng.repack(self.P, True, _s())
+        self.eng.train_pack_token = object()
         self.model._invalidate_eval_pack()
 
     def fit(self, maps, start, iters=50, lr=0.02, free=None, bounds=(0.0, 1.0), betas=(0.9, 0.999), eps=1e-8,
@@ -865,28 +834,12 @@ class ParamFit:
         M, K, ncf = st.shape
         score = torch.empty(M, K, dtype=torch.float64, device=self.dev)
         g = torch.empty(M, K, ncf, dtype=torch.float64, device=self.dev)
-        for sl, r in self._chunks(x, st, tg, z, int(n_noise), weight, int(seed), int(max_rows)):
+        R = int(n_noise)
+        for sl, r in self._chunks(x, st, tg, z, R, weight, int(seed), int(max_rows), R):
             r.positions()
             score[:, sl] = r.acc
             g[:, sl] = r.gacc.view(M, -1, ncf)
         return score, g
-
-    def _chunks(self, x, start, tg, z, R, weight, seed, max_rows):
-        """The chunk loop shared by :meth:`_fit` and :meth:`value_and_grad`: draws the shortcut rows (once, before any
-        chunk runs), refreshes the pack and the weight table, then yields (columns k0 .. k0 + kc of the starts, the
-        loaded run) for every chunk of Kc = max(1, max_rows // M) starts."""
-        M, K, _ = start.shape
-        npos = len(tg) * R
-        Kc = min(K, max(1, max_rows // M))
-        pos_t = torch.tensor(tg * R, dtype=torch.int32)                   # position p = r S + s
-        rows = torch.stack([_draw_shortcut_row(self.model.n_feat) for _ in range(npos)])
-        self._refresh()
-        self.w.copy_(self._wtab[weight])
-        for k0 in range(0, K, Kc):
-            kc = min(Kc, K - k0)
-            r = self._run(M, kc, npos, z is not None, R)
-            r.load(x, start[:, k0:k0 + kc], pos_t, rows, z, seed)
-            yield slice(k0, k0 + kc), r
 
     @torch.no_grad()
     def _fit(self, x, start, tg, z, mask, lo, hi, iters, lr, betas, eps, R, weight, seed, max_rows) -> FitResult:
@@ -898,7 +851,7 @@ class ParamFit:
         score, hist_s, hist_g = D(M, K), D(iters + 1, M, K), D(iters + 1, M, K)
         params, last = torch.empty(M, K, ncf, device=dev), torch.empty(M, K, ncf, device=dev)
         stalled = torch.empty(M, K, dtype=torch.int32, device=dev)
-        for sl, r in self._chunks(x, start, tg, z, R, weight, seed, max_rows):
+        for sl, r in self._chunks(x, start, tg, z, R, weight, seed, max_rows, R):
             kc = r.Kc
             hs, hg = D(iters + 1, M * kc), D(iters + 1, M * kc)
             r.run(iters, lr, betas[0], betas[1], eps, mask, lo, hi, bc, hs, hg)
@@ -909,16 +862,6 @@ class ParamFit:
             hist_s[:, :, sl] = hs.view(iters + 1, M, kc)
             hist_g[:, :, sl] = hg.view(iters + 1, M, kc)
         return FitResult(params, score, last, start.to(dev), hist_s, hist_g, stalled, tg, R, weight)
-
-
-def _fitter(model, timesteps, steps_per_graph=8, sched=None) -> ParamFit:
-    cache = model.__dict__.setdefault("_cdm_param_fit", {})
-    skey = None if sched is None else tuple(v.numpy().tobytes() for v in sched)
-    key = (int(timesteps), int(steps_per_graph), skey)
-    pf = cache.get(key)
-    if pf is None:
-        pf = cache[key] = ParamFit(model, timesteps, steps_per_graph, sched_tensors=sched)
-    return pf
 
 
 def param_fit(model, maps, start, timesteps, iters=50, lr=0.02, free=None, bounds=(0.0, 1.0), betas=(0.9, 0.999),
@@ -937,9 +880,10 @@ def param_fit(model, maps, start, timesteps, iters=50, lr=0.02, free=None, bound
     sched = _sched_tensors(timesteps, ab_t, b_t, None)
     checked = check_fit(maps, start, timesteps, model.n_cfeat, model.h, iters, lr, free, bounds, betas, eps, t_grid,
                         n_steps, n_noise, weight, noise, max_rows, model.in_channels)
-    return _fitter(model, timesteps, steps_per_graph, sched)._fit(
-        *checked, int(iters), float(lr), tuple(float(b) for b in betas), float(eps), int(n_noise), weight, int(seed),
-        int(max_rows))
+    pf = _cached(model, "_cdm_param_fit", (timesteps, int(steps_per_graph), sched),
+                 lambda: ParamFit(model, timesteps, steps_per_graph, sched_tensors=sched))
+    return pf._fit(*checked, int(iters), float(lr), tuple(float(b) for b in betas), float(eps), int(n_noise), weight,
+                   int(seed), int(max_rows))
 
 
 def calculate_elbo_and_bpd(*args, **kwargs):
