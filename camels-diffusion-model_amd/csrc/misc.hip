@@ -10,48 +10,9 @@
 //   torch.optim.Adam        code/train_diffusion_condition.py:200 (single-tensor Adam arithmetic)
 //   weight repacking        OIHW / [Cin][Cout][kh][kw] -> GEMM-ready layouts (+ eval-mode BN fold)
 #include "cdm_common.h"
+#include "sampler_parts.h"
 
 namespace cdm {
-
-static inline int nblocks(long long total, int per = 256, int cap = 8192) {
-    long long b = (total + per - 1) / per;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Philox4x32-10 (counter-based; used for training noise / timesteps and sampler z)
-// ------------------------------------------------------------------------------------------------
-struct U4 { uint32_t x, y, z, w; };
-static __device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                            uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-static __device__ __forceinline__ float u01(uint32_t v) { return ((float)(v >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-static __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = u01(a), u2 = u01(b);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c; sincosf(6.283185307179586f * u2, &s, &c);
-    z0 = r * c; z1 = r * s;
-}
-// normal for element e of stream `sub`
-static __device__ __forceinline__ float philox_normal(unsigned long long seed, uint32_t sub, long long e) {
-    const U4 v = philox((uint32_t)(e >> 2), (uint32_t)((unsigned long long)e >> 34), sub, 0x5EEDu,
-                        (uint32_t)seed, (uint32_t)(seed >> 32));
-    float z0, z1, z2, z3;
-    box_muller(v.x, v.y, z0, z1); box_muller(v.z, v.w, z2, z3);
-    const int j = (int)(e & 3);
-    return j == 0 ? z0 : (j == 1 ? z1 : (j == 2 ? z2 : z3));
-}
 
 __global__ void philox_uniform_kernel(float* out, long long n, float lo, float hi, unsigned long long seed, uint32_t sub,
                                       const int* sub_dev) {
@@ -1048,27 +1009,7 @@ __global__ void sample_prologue_kernel(int* ctr, int S, int T, const int* steps,
         for (int q = threadIdx.x; q < sc_row; q += blockDim.x) sc_cur[q] = sc_table[(long long)(S - k) * sc_row + q];
 }
 
-// The pieces the kernels that write the sampler state share; the arithmetic of each update stays in its kernel.
-// eps of a step: eu + w (ec - eu) when cfg (classifier-free guidance; model batch = 2n, cond half first), else eps[e].
-static __device__ __forceinline__ float cfg_eps(const float* eps, long long numel, long long e, int cfg, float w) {
-#pragma clang fp contract(off)  // per function, so needed here too: a fused w * (ep - eu) + eu is another rounding
-    const float ep = eps[e];
-    if (!cfg) return ep;
-    const float eu = eps[numel + e];
-    return eu + w * (ep - eu);
-}
-// per-run Philox key: seed ^ *seed_dev (drawn from torch's CUDA generator before every run, so consecutive sampling
-// calls get fresh z, as the reference's randn_like on the device does)
-static __device__ __forceinline__ unsigned long long run_key(unsigned long long seed, const long long* seed_dev) {
-    return seed_dev ? seed ^ (unsigned long long)seed_dev[0] : seed;
-}
-// Writes v into x and both halves of the model-input buffer (x2 may alias x), and a snapshot when slot >= 0.
-static __device__ __forceinline__ void store_state(float v, long long e, long long numel, float* x, float* x2, int slot,
-                                                   float* snaps) {
-    x[e] = v;
-    if (x2) { x2[e] = v; x2[numel + e] = v; }
-    if (slot >= 0) snaps[(long long)slot * numel + e] = v;
-}
+// cfg_eps, run_key, store_state, ddim_update and the Philox draws: sampler_parts.h (shared with csrc/guide.hip).
 
 // x <- (x - eps*coef[i]) / sa[i] + sb[i]*z ;  eps: cfg_eps
 // z = 0 at i == 1; z from z_table[(T-i)][e] when given, else Philox(run_key, stream i).
@@ -1097,9 +1038,8 @@ __global__ void denoise_kernel(const float* xin, float* x, float* x2, long long 
 // and the last position); else z_table[(S-k)][e] when given, else Philox(run_key, stream i) keyed by the timestep.
 // Write-out: store_state, slot[k].  A k outside 1..S writes nothing.
 // BY_POSITION (a position program, where one timestep is visited more than once: cdm_ddim_step_pos): the device z is
-// Philox keyed by run_key ^ STEP_NOISE_DOMAIN, stream k, so every visit draws its own; cur_i is not read.  The constant
-// is the ASCII of "pos_step" and has no other meaning.
-constexpr unsigned long long STEP_NOISE_DOMAIN = 0x706F735F73746570ull;
+// Philox keyed by run_key ^ STEP_NOISE_DOMAIN (sampler_parts.h), stream k, so every visit draws its own; cur_i is not
+// read.
 template <bool BY_POSITION>
 __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg,
                                  float w, const int* cur_i, const int* cur_k, const float* cx, const float* ce,
@@ -1113,11 +1053,8 @@ __global__ void ddim_step_kernel(const float* xin, float* x, float* x2, long lon
     const int slot = snap_slot ? snap_slot[k] : -1;
     const unsigned long long sd = BY_POSITION ? run_key(seed, seed_dev) ^ STEP_NOISE_DOMAIN : run_key(seed, seed_dev);
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long long)gridDim.x * blockDim.x) {
-        float v = a * xin[e] + c * cfg_eps(eps, numel, e, cfg, w);
-        if (sg != 0.f) {
-            const float z = z_table ? z_table[(long long)(S - k) * zstride + e] : philox_normal(sd, (uint32_t)i, e);
-            v = v + sg * z;
-        }
+        const float v = ddim_update(xin[e], cfg_eps(eps, numel, e, cfg, w), a, c, sg, z_table, S - k, zstride, sd,
+                                    (uint32_t)i, e);
         store_state(v, e, numel, x, x2, slot, snaps);
     }
 }

@@ -38,6 +38,11 @@ Position programs (not in the reference): the strided samplers take ``resample=`
 masked run) and ``t_start=`` (a late start, SDEdit; ``DDPM.refine`` is its entry point) and then walk the positions of
 :func:`resample_program` with per-position tables, a DDIM step keyed by the position and ``cdm_mask_blend_jump``
 (:class:`_StridedSampler` has the definition).
+
+Observation-guided sampling (not in the reference): ``DDPM.reconstruct`` draws maps consistent with a coarse, noisy,
+partly missing observation (``degrade`` makes one): :class:`GuidedDDIMSampler` follows every DDIM step with a step down
+the image gradient of the weighted misfit of the data prediction, one frozen forward and one full backward per position
+on the step graph (``cdm_obs_residual_grad``, ``cdm_ddim_step_guided``).
 """
 from __future__ import annotations
 
@@ -374,6 +379,22 @@ def known_tables(ab_t):
     return sab.astype(np.float32), somab.astype(np.float32)
 
 
+def guided_tables(ab_t, taus):
+    """(sq, ra) of observation-guided sampling: sqrt(1 - ab_i) and 1 / sqrt(ab_i) at i = tau_p, fp32 numpy arrays of
+    S + 1 entries indexed by the position p = 1..S (entry 0 is the unused 0, 1), so that the data prediction of a state is
+    x0h = (x - sq[p] eps) ra[p] (:func:`dpmpp_tables`' first two tables).  ``ab_t`` is the fp32 table of the Schedule;
+    the arithmetic is fp64 numpy, rounded once to fp32.  Pure host function.  Raises ValueError for an invalid ``taus``
+    (:func:`timestep_subsequence`) and for a schedule that gives a non-finite entry (ab_t must lie in (0, 1])."""
+    ab = _ab64(ab_t)
+    tau = timestep_subsequence(ab.size - 1, None, taus)
+    ab_i = ab[np.array(tau, dtype=np.int64)]
+    with np.errstate(divide="ignore", invalid="ignore"):     # reported below
+        sq, ra = np.sqrt(1 - ab_i), 1 / np.sqrt(ab_i)
+    if not (np.isfinite(sq).all() and np.isfinite(ra).all()):
+        raise ValueError("the schedule gives non-finite guidance tables (ab_t must lie in (0, 1] for t >= 1)")
+    return (np.concatenate([[0.0], sq]).astype(np.float32), np.concatenate([[1.0], ra]).astype(np.float32))
+
+
 class Program(NamedTuple):
     """A position program (:func:`resample_program`): arrays of P + 1 entries indexed by the position p = P..1 in the
     order it runs, entry 0 unused."""
@@ -576,6 +597,69 @@ def check_inpaint(known, mask, n: int, H: int, known_noise: str = "fixed", in_ch
     return known, mask
 
 
+OBS_FACTORS = (1, 2, 4, 8)
+
+
+def check_observation(obs, weight, n: int, H: int, factor: int = 4, zeta: float = 1.0, in_channels: int = 1):
+    """Validate the inputs of observation-guided sampling -> (obs [n,1,h,h], weight [n or 1,1,h,h]) with h = H / factor,
+    as given (any device); ``weight`` None is the plane of ones [1,1,h,h].  ``obs`` and ``weight`` may come without the
+    channel axis.  ValueError, before anything is allocated: a model with in_channels > 1; ``factor`` not in
+    {1, 2, 4, 8} or not dividing H; ``zeta`` negative or not finite; a shape other than those; a non-floating array; a
+    weight negative or non-finite; ``obs`` non-finite where the weight is > 0 (where it is 0 the cell is not observed and
+    may hold anything)."""
+    if in_channels != 1:
+        raise ValueError("observation-guided sampling is single-channel, like the samplers: the model has in_channels "
+                         f"= {in_channels}")
+    if isinstance(factor, bool) or factor not in OBS_FACTORS:
+        raise ValueError(f"factor must be one of {OBS_FACTORS}, got {factor!r}")
+    if H % factor != 0:
+        raise ValueError(f"factor = {factor} does not divide the map size {H}")
+    if isinstance(zeta, bool) or not np.isfinite(zeta) or not zeta >= 0:
+        raise ValueError(f"zeta must be finite and >= 0, got {zeta!r}")
+    if obs is None:
+        raise ValueError("observation-guided sampling needs obs=")
+    h = H // factor
+    obs = torch.as_tensor(obs)
+    if obs.dim() == 3:
+        obs = obs[:, None]
+    if tuple(obs.shape) != (n, 1, h, h):
+        raise ValueError(f"obs must have shape {(n, 1, h, h)} (H / factor = {h}), got {tuple(obs.shape)}")
+    if weight is None:
+        weight = torch.ones(1, 1, h, h)
+    weight = torch.as_tensor(weight)
+    if weight.dim() == 3:
+        weight = weight[:, None]
+    if tuple(weight.shape) not in ((n, 1, h, h), (1, 1, h, h)):
+        raise ValueError(f"weight must have shape {(n, 1, h, h)} or {(1, 1, h, h)}, got {tuple(weight.shape)}")
+    if not (obs.is_floating_point() and weight.is_floating_point()):
+        raise ValueError("obs and weight must be floating-point arrays")
+    if not bool(((weight >= 0) & torch.isfinite(weight)).all()):          # NaN fails the comparison
+        raise ValueError("weight values must be finite and >= 0")
+    if not bool(torch.isfinite(obs)[(weight > 0).expand_as(obs)].all()):
+        raise ValueError("obs holds a non-finite value where weight > 0")
+    return obs, weight
+
+
+def degrade(maps, factor: int, sigma: float = 0.0, seed: Optional[int] = None):
+    """An observation of ``maps`` [n,1,H,H] (or [n,H,H]) as :class:`GuidedDDIMSampler` models one: the ``factor`` x
+    ``factor`` block mean plus ``sigma`` times standard normal noise from a CPU generator seeded with ``seed`` (None: the
+    global CPU RNG) -> [n,1,H/factor,H/factor] fp32 on the CPU.  A convenience on torch ops, not a kernel."""
+    maps = torch.as_tensor(maps).detach().to("cpu", torch.float32)
+    if maps.dim() == 3:
+        maps = maps[:, None]
+    if maps.dim() != 4 or maps.shape[1] != 1 or maps.shape[2] != maps.shape[3]:
+        raise ValueError(f"maps must have shape [n, 1, H, H], got {tuple(maps.shape)}")
+    if isinstance(factor, bool) or factor not in OBS_FACTORS or maps.shape[2] % factor != 0:
+        raise ValueError(f"factor must be one of {OBS_FACTORS} and divide the map size {maps.shape[2]}, got {factor!r}")
+    if not np.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"sigma must be finite and >= 0, got {sigma!r}")
+    y = torch.nn.functional.avg_pool2d(maps, factor)
+    if sigma > 0:
+        g = None if seed is None else torch.Generator().manual_seed(int(seed))
+        y = y + float(sigma) * torch.randn(y.shape, generator=g)
+    return y
+
+
 class GraphSampler:
     """One reverse-diffusion run (T steps) of ContextUnet on the HIP engine, hipGraph-replayed.
 
@@ -623,9 +707,8 @@ class GraphSampler:
         B = 2 * n if self.cfg else n
         self.B = B
         self.sets = 2 if self.cfg else 1
-        s = _s()
-        eng.repack(P, False, s, key=model._eval_pack_key(P))
-        self.ws = eng.workspace(B, False)
+        self._repack()
+        self.ws = self._workspace()
         E = lambda *sh: torch.empty(*sh, device=dev)
         self.xbuf = E(B, H, H)
         self.cbuf = torch.zeros(B, ncf, device=dev)
@@ -656,6 +739,17 @@ class GraphSampler:
             self.ksab, self.ksomab = (torch.from_numpy(v).to(dev) for v in ktab)
             if z_source == "host":
                 self.xi_table = E(1 if inpaint == "fixed" else max(self.npos - 1, 1), n * H * H)
+
+    def _repack(self):
+        """Refresh the weight pack the step's forward runs on (the eval pack, unless a subclass says otherwise)."""
+        self.eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+
+    def _workspace(self):
+        return self.eng.workspace(self.B, False)
+
+    def _rehome(self, P):
+        """The parameters moved to the tensors ``P``: the captured graph holds the old addresses."""
+        self.P, self.graph = P, None
 
     def _draws_host_z(self, p: int) -> bool:
         """Whether position p of npos..1 takes a z from the CPU RNG in a host_z run (the solver's own rule)."""
@@ -731,11 +825,11 @@ class GraphSampler:
         self._step(s)
 
     def prepare(self):
-        """Refresh the eval weight pack and capture the step graph (idempotent)."""
+        """Refresh the weight pack and capture the step graph (idempotent)."""
         P = _rehomed(self.model, self.P)
         if P is not None:
-            self.P, self.graph = P, None                    # parameters were re-homed: re-capture
-        self.eng.repack(self.P, False, _s(), key=self.model._eval_pack_key(self.P))
+            self._rehome(P)                                 # parameters were re-homed: re-capture
+        self._repack()
         if self.use_graph and self.graph is None and self.npos >= self.K:
             self.graph = _capture_steps(self._warm_up, self._step, self.K)
 
@@ -928,6 +1022,120 @@ class DPMSolverSampler(_StridedSampler):
         lib().cdm_dpmpp_step(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
                              1 if self.cfg else 0, self.guide_w, _p(self.cur_k), *(_p(t) for t in self.tables), self.npos,
                              _p(self.dprev), _p(self.slot), _p(self.snaps), s)
+
+
+class GuidedDDIMSampler(_StridedSampler):
+    """Strided DDIM sampling guided by a coarse, noisy, partly missing observation (diffusion posterior sampling, Chung
+    et al. 2023; not in the reference; DESIGN §1 has the definition).
+
+    Observation model y = A x0 + n: A the f x f block mean [H, H] -> [H / f, H / f], ``weight`` [n or 1, H / f, H / f] a
+    relative inverse variance per cell, 0 = not observed.  At the position p = S..1 of the plain walk over ``taus``:
+        eps    = the frozen train-structured forward (model.eval()'s forward kept for a backward), CFG-combined
+        x0h    = (x - sq[p] eps) ra[p];   r = y - A x0h;   L[s] = sum_q wgt_q r_q^2          (``cdm_obs_residual_grad``)
+        grad   = dL/dx = A^T-term through x0h directly + the engine's full backward of dL/d eps (``dx=``)
+        x     <- DDIM step of p - (zeta / (2 sqrt(L[s]))) grad                               (``cdm_ddim_step_guided``)
+    a step of length ``zeta`` down the gradient of the misfit norm sqrt(L) after every DDIM step.  ``zeta`` = 0 launches
+    neither the backward nor the gradient outputs and is the DDIM step bit for bit; L is still recorded.  ``hist``
+    [S + 1, n] fp64 keeps L by position (row p).
+
+    The sampler runs on the engine's train pack and a frozen workspace ``eng.workspace(B, True, frozen=True)``, which
+    keeps the fp32 activations of all B rows for the backward: n is bounded by memory.  As :class:`ParamFit` does, it
+    renews the pack token and invalidates the model's eval pack, so a Trainer, an autograd backward or an eval call
+    sharing the engine afterwards repacks its own weights.  ``run(x_T, obs=, weight=)`` copies the two arrays into
+    buffers allocated here once, so the captured graph serves any contents.  Device z is keyed by the position, in
+    ``cdm_ddim_step_pos``'s key domain; the host z table goes by row S - p.  CPU-RNG order: :class:`DDIMSampler`'s."""
+
+    def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor],
+                 steps=50, eta: float = 0.0, spacing="uniform", save_rate: int = 20, z_source: str = "device",
+                 steps_per_graph: int = 10, seed: int = 1234, snapshots: bool = True, use_graph: bool = True,
+                 factor: int = 4, weight_n: int = 1, zeta: float = 1.0):
+        taus = timestep_subsequence(sched.T, steps, spacing)
+        self.eta, self.zeta, self.factor = float(eta), float(zeta), int(factor)
+        tables = ddim_tables(sched.ab_t, taus, self.eta)                   # validates before anything is allocated
+        gtab = guided_tables(sched.ab_t, taus)
+        H = model.h
+        if isinstance(factor, bool) or factor not in OBS_FACTORS or H % factor != 0:
+            raise ValueError(f"factor must be one of {OBS_FACTORS} and divide the map size {H}, got {factor!r}")
+        if not np.isfinite(self.zeta) or self.zeta < 0:
+            raise ValueError(f"zeta must be finite and >= 0, got {zeta!r}")
+        if weight_n not in (1, n):
+            raise ValueError(f"weight_n must be 1 or n = {n}, got {weight_n}")
+        if model.in_channels != 1:
+            raise ValueError(f"observation-guided sampling is single-channel: the model has in_channels = "
+                             f"{model.in_channels}")
+        super().__init__(model, sched, n, guide_w, params, taus, save_rate, z_source, steps_per_graph, seed, snapshots,
+                         use_graph, None, None, None)
+        dev, B = self.dev, self.B
+        self.K = min(self.K, self.npos)                      # a short walk is one graph
+        self.cx, self.ce, self.sigma = (torch.from_numpy(v).to(dev) for v in tables)
+        self.sq, self.ra = (torch.from_numpy(v).to(dev) for v in gtab)
+        cells = (H // self.factor) ** 2
+        self.weight_n = int(weight_n)
+        self.obs = torch.zeros(n * cells, device=dev)
+        self.wgt = torch.zeros(self.weight_n * cells, device=dev)
+        self.L = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.hist = torch.zeros(self.npos + 1, n, dtype=torch.float64, device=dev)
+        # the closing misfit of the final x itself: x0h = x (tables sq = 0, ra = 1 of a one-position walk)
+        self.one = torch.ones(1, dtype=torch.int32, device=dev)
+        self.sq0, self.ra1 = torch.zeros(2, device=dev), torch.ones(2, device=dev)
+        self.last = torch.zeros(2, n, dtype=torch.float64, device=dev)
+        self.deps = self.gdir = self.dx = None
+        if self.zeta > 0:
+            self.deps, self.gdir, self.dx = (torch.empty(B, H, H, device=dev), torch.empty(n, H, H, device=dev),
+                                             torch.empty(B, H, H, device=dev))
+        self._rehome(self.P)
+
+    def _repack(self):
+        self.eng.repack(self.P, True, _s())
+        self.eng.train_pack_token = object()
+        self.model._invalidate_eval_pack()
+
+    def _workspace(self):
+        return self.eng.workspace(self.B, True, frozen=True)
+
+    def _rehome(self, P):
+        super()._rehome(P)
+        # scratch parameter gradients of the backward (written, never read)
+        self.G = {k: torch.empty_like(P[k]) for k in self.model._param_names} if self.zeta > 0 else None
+
+    def _draws_host_z(self, p):
+        return self.eta > 0 and p > 1
+
+    def _residual(self, s, x, eps, cfg, cur_k, sq, ra, npos, hist, deps, gdir):
+        lib().cdm_obs_residual_grad(_p(x), _p(eps), 1 if cfg else 0, self.guide_w, _p(self.obs), _p(self.wgt),
+                                    self.wgt.numel(), self.n, self.H, self.factor, _p(cur_k), _p(sq), _p(ra), npos,
+                                    _p(self.L), _p(hist), _p(deps), _p(gdir), s)
+
+    def _step(self, s):
+        self._prologue(s)
+        half = self.sets * self.model.n_feat
+        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, self.sc_cur[:half], self.sc_cur[half:],
+                               self.n, s, frozen=True)
+        self._residual(s, self.xbuf, eps, self.cfg, self.cur_k, self.sq, self.ra, self.npos, self.hist, self.deps,
+                       self.gdir)
+        if self.zeta > 0:
+            self.eng.backward(self.ws, self.P, self.deps, self.G, s, dx=self.dx)
+        numel = self.n * self.H * self.H
+        lib().cdm_ddim_step_guided(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                                   1 if self.cfg else 0, self.guide_w, _p(self.cur_k), _p(self.cx), _p(self.ce),
+                                   _p(self.sigma), self.npos, _p(self.z_table), numel, self.seed, _p(self.zseed),
+                                   _p(self.slot), _p(self.snaps), _p(self.gdir), _p(self.dx), _p(self.L), self.zeta,
+                                   self.H, s)
+
+    def run(self, x_T: torch.Tensor, steps: Optional[int] = None, obs=None, weight=None):
+        """Every position (or the first ``steps``) from x_T [n,1,H,H] under the observation ``obs`` [n,1,h,h] and
+        ``weight`` [weight_n,1,h,h] (both required, copied into this sampler's buffers; :func:`check_observation` is the
+        caller's validation) -> (x [n,1,H,H], intermediate np [slots,n,1,H,H] or None, misfit [S + 1, n] fp64 on the
+        host): misfit[S - p] = sqrt(L) seen at position p, the last row sqrt(L) of the final x itself."""
+        if obs is None or weight is None:
+            raise ValueError("a guided sampler needs obs= and weight=")
+        self.obs.copy_(torch.as_tensor(obs).to(self.dev, torch.float32).reshape(-1))
+        self.wgt.copy_(torch.as_tensor(weight).to(self.dev, torch.float32).reshape(-1))
+        self.hist.zero_()
+        x, inter = super().run(x_T, steps)
+        self._residual(_s(), self.xbuf, self.xbuf, False, self.one, self.sq0, self.ra1, 1, self.last, None, None)
+        L = torch.cat([self.hist[1:].flip(0), self.last[1:]])
+        return x, inter, L.sqrt().cpu()
 
 
 PLAIN = (1, 1, None)          # (resample, jump, t_start) of the plain walk: no position program
@@ -1125,6 +1333,59 @@ class DDPM:
         a, b = sab[t0].to(dev), somab[t0].to(dev)
         x = a * init.to(dev, torch.float32) + b * torch.as_tensor(noise).to(dev, torch.float32)
         return fn(x, params, guide_w=guide_w, known=known, mask=mask, t_start=t_start, **sampler_kwargs)
+
+    @torch.no_grad()
+    def reconstruct(self, obs, params=None, guide_w=0.0, factor=4, weight=None, zeta=1.0, steps=50, eta=0.0,
+                    spacing="uniform", noise=None, save_rate=20, z_source=None, **unsupported):
+        """Draw full-resolution maps consistent with the coarse, noisy observation ``obs`` [n,1,H/factor,H/factor] (and
+        with ``params``, under CFG when ``guide_w`` > 0) -> (x [n,1,H,H], intermediates, misfit [S + 1, n] fp64).
+
+        :class:`GuidedDDIMSampler` has the definition: y = A x0 + n with A the ``factor`` x ``factor`` block mean and
+        ``weight`` [n or 1,1,h,h] the relative inverse variance of every cell (0 = not observed, the way to mask; None =
+        all ones); after every DDIM step of the ``steps`` positions (``eta``, ``spacing`` as :meth:`sample_ddim`) the
+        state takes a step of length ``zeta`` down the gradient of the misfit norm.  misfit[S - p] = sqrt(L) seen at
+        position p, the last row that of the returned x itself.  ``noise`` [n,1,H,H] fixes x_T (drawn from the CPU RNG
+        when None); ``params`` None runs without context.  ``z_source`` None: this object's.  Costs, per position, one
+        frozen forward and one full backward of B rows (B = 2 n with CFG) against the plain sampler's eval forward, and
+        the frozen workspace's fp32 activations of B rows.  Samplers are cached per configuration, as :meth:`_sampler`
+        does; the contents of obs / weight are not part of the key.  ValueError, before anything is drawn or allocated:
+        what :func:`check_observation` lists, and any of sampler= (other than "ddim"), resample / jump / t_start,
+        known / mask: guided sampling is the plain DDIM walk, and a zero weight is how a pixel is left unobserved."""
+        if unsupported.pop("sampler", "ddim") != "ddim":
+            raise ValueError('observation-guided sampling is sampler="ddim" only: "ddpm" is its eta=1.0 on all T steps, '
+                             'and the multistep "dpmpp" history does not survive the guidance step')
+        for k in ("resample", "jump", "t_start", "known", "mask"):
+            if k in unsupported:
+                raise ValueError(f"observation-guided sampling takes no {k}=: it runs the plain walk, and weight = 0 "
+                                 "marks an unobserved cell")
+        if unsupported:
+            raise TypeError(f"reconstruct() got unexpected keyword arguments {sorted(unsupported)}")
+        H = self.model.h
+        obs_t = torch.as_tensor(obs) if obs is not None else None
+        if obs_t is None or obs_t.dim() not in (3, 4):
+            raise ValueError("obs must have shape [n, 1, H / factor, H / factor]")
+        n = obs_t.shape[0]
+        obs_t, wgt = check_observation(obs_t, weight, n, H, factor, zeta, self.model.in_channels)
+        if noise is not None and tuple(torch.as_tensor(noise).shape) != (n, 1, H, H):
+            raise ValueError(f"noise must have shape {(n, 1, H, H)}, got {tuple(torch.as_tensor(noise).shape)}")
+        zs = self.z_source if z_source is None else z_source
+        if zs not in ("device", "host"):
+            raise ValueError(f'z_source must be "device" or "host", got {zs!r}')
+        taus = timestep_subsequence(self.T, steps, spacing)
+        ddim_tables(self.sched.ab_t, taus, eta)
+        x_T = torch.randn(n, 1, H, H) if noise is None else torch.as_tensor(noise)
+        key = ("guided", n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, zs, steps,
+               float(eta), spacing if isinstance(spacing, str) else tuple(spacing), int(factor), int(wgt.shape[0]),
+               float(zeta))
+        smp = self._samplers.get(key)
+        if smp is None:
+            smp = self._samplers[key] = GuidedDDIMSampler(self.model, self.sched, n, guide_w, params, steps, eta, spacing,
+                                                          save_rate, zs, seed=self.seed, factor=int(factor),
+                                                          weight_n=int(wgt.shape[0]), zeta=float(zeta))
+        elif params is not None:
+            smp.cbuf[:n] = params.to(smp.dev, torch.float32).reshape(n, -1)
+        smp.prepare_rng(host_z=zs == "host")
+        return smp.run(x_T, obs=obs_t, weight=wgt)
 
     def param_scan(self, maps, candidates, **kwargs):
         """:func:`cdm_amd.param_scan` of this model under this schedule: ``score[m, k]`` of every map under every

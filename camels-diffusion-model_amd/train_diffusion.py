@@ -55,6 +55,14 @@ Training for guided sampling (all off by default; without them the outputs are t
   --refine-init PATH.npy --refine-t-start T0
                  with --sample-steps: noise the --n-samples maps of the file to the level of the largest sampled
                  timestep <= T0 and denoise from there (late start); writes refined_samples.npy and a "Refinement" line.
+  --observe PATH.npy --observe-factor F [--observe-weight PATH.npy --observe-zeta Z]
+                 with --sample-steps (DDIM): draw --n-samples full-resolution maps consistent with the coarse, noisy
+                 observation of the file ([n,H/F,W/F] or [n,1,H/F,W/F], normalised data units; F in 1, 2, 4, 8) by
+                 observation-guided sampling (cdm_amd.DDPM.reconstruct): after every DDIM step a step of length Z
+                 (default 1) down the gradient of the weighted misfit norm; the weight file ([n or 1,H/F,W/F], >= 0,
+                 0 = not observed) defaults to ones.  Writes reconstructed_samples.npy and reconstruct_misfit.npy
+                 ([S+1,n]: the misfit norm seen at every position, then that of the written maps); the log gets an
+                 "Observation-guided" line.
   --scan-maps PATH.npy --scan-candidates PATH.npy [--scan-steps S --scan-noise R --scan-weight uniform|nll]
                  conditioned runs only: after the sampling above, score every map of the first file (arrays [M,H,W] or
                  [M,1,H,W], normalised data units) under every parameter vector of the second ([K,NUM_PARAMS], normalised
@@ -112,6 +120,18 @@ def load_inpaint(known_path, mask_path, n, H):
     if known.shape[0] != n:
         raise ValueError(f"known holds {known.shape[0]} maps, --n-samples is {n}")
     return check_inpaint(known, mask, n, H)
+
+
+def load_observation(obs_path, weight_path, n, H, factor, zeta):
+    """The --observe / --observe-weight files as fp32 tensors (obs [n,1,h,h], weight [n or 1,1,h,h], h = H / factor;
+    no weight file: ones).  ValueError for what cdm_amd.check_observation rejects."""
+    from cdm_amd.diffusion import check_observation
+    obs = np.load(obs_path, allow_pickle=False)
+    wgt = None if weight_path is None else np.load(weight_path, allow_pickle=False)
+    if wgt is not None and wgt.ndim == 2:
+        wgt = wgt[None]
+    as_t = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))   # noqa: E731
+    return check_observation(as_t(obs), as_t(wgt), n, H, factor, zeta)
 
 
 def load_maps(path, n, H):
@@ -172,6 +192,13 @@ def main(argv=None):
                     help="maps [n,H,W] or [n,1,H,W] (normalised data units) to re-draw from --refine-t-start; n = --n-samples")
     ap.add_argument("--refine-t-start", type=int, default=None, metavar="T0",
                     help="the timestep --refine-init is noised to (the largest sampled timestep <= T0)")
+    ap.add_argument("--observe", default=None, metavar="PATH.npy",
+                    help="coarse observation [n,H/F,W/F] or [n,1,H/F,W/F] (normalised data units); n = --n-samples")
+    ap.add_argument("--observe-factor", type=int, default=None, metavar="F", help="block size of --observe: 1, 2, 4 or 8")
+    ap.add_argument("--observe-weight", default=None, metavar="PATH.npy",
+                    help="per-cell weight [n,H/F,W/F], [n,1,H/F,W/F] or [H/F,W/F], >= 0: relative inverse variance, 0 = not "
+                         "observed (default: ones)")
+    ap.add_argument("--observe-zeta", type=float, default=1.0, metavar="Z", help="guidance step length of --observe")
     ap.add_argument("--scan-maps", default=None, metavar="PATH.npy",
                     help="maps [M,H,W] or [M,1,H,W] (normalised data units) to score under --scan-candidates")
     ap.add_argument("--scan-candidates", default=None, metavar="PATH.npy",
@@ -254,6 +281,19 @@ def main(argv=None):
         ap.error("--inpaint-resample / --inpaint-jump need --inpaint-known, --inpaint-mask and --sample-steps S")
     if a.inpaint_resample < 1 or a.inpaint_jump < 1:
         ap.error("--inpaint-resample and --inpaint-jump must be >= 1")
+    a.observation = None
+    if a.observe is None and (a.observe_factor is not None or a.observe_weight is not None):
+        ap.error("--observe-factor / --observe-weight need --observe")
+    if a.observe is not None:
+        if a.observe_factor is None:
+            ap.error("--observe needs --observe-factor F")
+        if a.sample_steps == 0 or a.sampler != "ddim":
+            ap.error("--observe needs --sample-steps S with the DDIM sampler (guided sampling is a strided DDIM walk)")
+        try:
+            a.observation = load_observation(a.observe, a.observe_weight, a.n_samples, a.height, a.observe_factor,
+                                             a.observe_zeta)
+        except (OSError, ValueError) as e:
+            ap.error(f"--observe / --observe-weight: {e}")
     if (a.refine_init is None) != (a.refine_t_start is None):
         ap.error("--refine-init and --refine-t-start go together")
     a.refine = None
@@ -486,6 +526,18 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
         dt = time.time() - t0
         np.save(os.path.join(out_dir, "refined_samples.npy"), refined.cpu().numpy())
         log.write(f"Refinement of {ns} maps from t_start={a.refine_t_start} (w={a.guide_w}), {how}: {dt:.2f} s\n")
+    if a.observation is not None:
+        obs, wgt = a.observation
+        t0 = time.time()
+        recon, _, misfit = d.reconstruct(obs, p, a.guide_w, factor=a.observe_factor, weight=wgt, zeta=a.observe_zeta,
+                                         **ddim)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        np.save(os.path.join(out_dir, "reconstructed_samples.npy"), recon.cpu().numpy())
+        np.save(os.path.join(out_dir, "reconstruct_misfit.npy"), misfit.numpy())
+        log.write(f"Observation-guided sampling of {ns} maps (w={a.guide_w}, factor={a.observe_factor}, "
+                  f"zeta={a.observe_zeta:g}, {float((wgt > 0).float().mean()):.3f} of the cells observed), {how}: "
+                  f"final misfit {', '.join(f'{v:.4g}' for v in misfit[-1].tolist())}: {dt:.2f} s\n")
     if a.scan is not None:
         smaps, scand, tg = a.scan
         t0 = time.time()

@@ -545,6 +545,41 @@ int cdm_mask_blend_jump(float* x, float* x2, long long numel, const float* known
                         const float* fa, const float* fb, const float* xi_table, long long xistride, int fresh,
                         const float* zeta_table, long long zetastride, unsigned long long seed,
                         const long long* seed_dev, const int* snap_slot, float* snaps, void* stream);
+/* Observation-guided sampling (diffusion.GuidedDDIMSampler, not in the reference; csrc/guide.hip): diffusion posterior
+ * sampling against y = A x0 + n, A the f x f block mean [H, H] -> [H / f, H / f], with a per-cell weight.  A step is
+ * cdm_sample_prologue_sub, the frozen train-structured forward, cdm_obs_residual_grad, the engine's full backward with
+ * dx, and cdm_ddim_step_guided.  Neither kernel synchronises or allocates.
+ * cdm_obs_residual_grad, at the position p = *cur_k (sq / ra [npos + 1]: sqrt(1 - ab_i) and 1 / sqrt(ab_i) by position,
+ * diffusion.guided_tables), each line one fp32 rounding unless marked (eps = eu + w (ec - eu) when cfg):
+ *   x0h_e = (x_e - sq[p] eps_e) * ra[p]
+ *   m_q   = (the f f x0h of cell q added in row-major order) * (1 / f^2);   r_q = obs_q - m_q
+ *   L[s]  = sum_q ((double)wgt_q (double)r_q) (double)r_q    fp64, assigned; hist[p n + s] = L[s]  (hist [npos + 1][n])
+ *   u_e   = (wgt_q r_q) * (1 / f^2) for every pixel e of cell q
+ *   gdir_e = (float)(-2 (double)ra[p]) u_e;   ge_e = (float)(2 (double)sq[p] (double)ra[p]) u_e
+ *   deps_e = ge_e;  with cfg: w ge_e on the cond row, (1 - w) ge_e on the uncond row (deps [n or 2 n][H H])
+ * x [n][H][H], eps [n or 2 n][H][H], obs [n][H / f][H / f]; wgt_q = wgt[(s cells + q) % wgt_numel], so a weight plane of
+ * one sample serves the batch.  A cell with wgt_q == 0 is not observed: obs_q is not read, u = 0, nothing added to L.
+ * One block per sample, one thread owns whole cells; per-thread fp64 sums over a fixed cell set (q = t, t + 256, ...),
+ * a wave64 butterfly, a fixed-order fold of the four wave sums through LDS: two runs give the same bits; no atomics.
+ * deps and gdir both null: only L and hist are written (the zeta == 0 form).  A p outside 1..npos writes nothing.
+ * hipErrorInvalidValue, nothing launched: a required pointer null; n, H or npos < 1; f not in {1, 2, 4, 8}; H % f != 0;
+ * wgt_numel neither the cell count nor n times it; exactly one of deps and gdir null. */
+int cdm_obs_residual_grad(const float* x, const float* eps, int cfg, float w, const float* obs, const float* wgt,
+                          long long wgt_numel, int n, int H, int f, const int* cur_k, const float* sq, const float* ra,
+                          int npos, double* L, double* hist, float* deps, float* gdir, void* stream);
+/* cdm_ddim_step_pos (its update, position-keyed z, host-z row and write-out) followed by a step of length zeta down the
+ * gradient of the misfit norm sqrt(L), with separate fp32 roundings (s = e / H^2, the sample):
+ *   grad_e = (grad_dir_e + dx_e) (+ dx_{numel + e} when cfg)
+ *   k_s    = (float)((double)zeta / (2 sqrt(L[s])));   x <- ((cx[k] x + ce[k] eps) + sigma[k] z) - k_s grad_e
+ * Where L[s] == 0, and everywhere when zeta == 0, nothing is subtracted and x has cdm_ddim_step_pos's bits; with
+ * zeta == 0 grad_dir, dx and L are not read and may be null.  dx [numel or 2 numel]: the engine backward's image
+ * gradient.  hipErrorInvalidValue, nothing launched: what cdm_ddim_step_pos rejects; H < 1; numel % H^2 != 0; zeta
+ * negative or not finite; zeta > 0 with grad_dir, dx or L null. */
+int cdm_ddim_step_guided(const float* xin, float* x, float* x2, long long numel, const float* eps, int cfg, float w,
+                         const int* cur_k, const float* cx, const float* ce, const float* sigma, int npos,
+                         const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
+                         const int* snap_slot, float* snaps, const float* grad_dir, const float* dx, const double* L,
+                         float zeta, int H, void* stream);
 /* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
