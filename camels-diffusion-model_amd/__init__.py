@@ -6,9 +6,11 @@ repo-root ``cdm_amd.py`` shim maps the hyphenated directory to that name).
 """
 from ._lib import lib  # noqa: F401
 from .augment import augment_maps, augment_source_index, check_augment_ops, draw_augment_ops  # noqa: F401
-from .diffusion import (DDPM, DDIMSampler, DPMSolverSampler, GraphSampler, GuidedDDIMSampler, Program,  # noqa: F401
-                        Schedule, check_inpaint, check_observation, ddim_tables, ddim_tables_from_pairs, degrade,
-                        denoise_add_noise, dpmpp_tables, dpmpp_tables_from_pairs, guided_tables, known_tables, perturb_input, resample_program, sample_ddpm,
+from .diffusion import (DDPM, DDIMEncoder, DDIMSampler, DPMSolverSampler, FlowLikelihood, FlowResult,  # noqa: F401
+                        GraphSampler, GuidedDDIMSampler, Program, Schedule, check_flow, check_inpaint,
+                        check_observation, ddim_tables, ddim_tables_from_pairs, degrade, denoise_add_noise,
+                        dpmpp_tables, dpmpp_tables_from_pairs, encode, encode_tables, flow_run_key, guided_tables,
+                        known_tables, log_likelihood, perturb_input, resample_program, sample_ddpm,
                         timestep_subsequence)
 from .likelihood import (FitResult, LikelihoodEvaluator, ParamFit, ParamScan, ScanResult,  # noqa: F401
                          calculate_elbo_and_bpd, calculate_elbo_and_bpd_batch, calculate_elbo_and_bpd_dataset,
@@ -28,4 +30,5 @@ __all__ = ["ContextUnet", "EmbedFC", "ResidualConvBlock", "UnetDown", "UnetUp", 
            "calculate_power_spectrum_2d", "compare_distributions", "pdfs", "augment_maps", "draw_augment_ops",
            "augment_source_index", "check_augment_ops", "param_scan", "param_grid", "ParamScan", "ScanResult",
            "check_scan", "param_fit", "ParamFit", "FitResult", "check_fit", "GuidedDDIMSampler", "guided_tables",
-           "check_observation", "degrade"]
+           "check_observation", "degrade", "DDIMEncoder", "FlowLikelihood", "FlowResult", "check_flow", "encode",
+           "encode_tables", "flow_run_key", "log_likelihood"]

@@ -9,12 +9,6 @@
 
 namespace cdm {
 
-static __device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One block per sample; thread t owns the cells t, t + 256, ... of the sample's (H / F)^2 cells, so the F x F mean and
 // its adjoint never cross threads.  At the position p = *cur_k, with s = sq[p], r = ra[p], each line one fp32 rounding:
 //   x0h_e = (x_e - s eps_e) * r                        eps: cfg_eps

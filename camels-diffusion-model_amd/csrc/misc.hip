@@ -877,12 +877,6 @@ __global__ __launch_bounds__(256) void mse_accum_kernel(const float* pred, const
     }
 }
 
-static __device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Parameter scan (likelihood.ParamScan): one map scored under K candidate contexts on common noise.
 // Prologue of a scan step, table-driven: the device counter holds the position p = 0..npos-1, counting up, and a
 // timestep may repeat (pos_t[p], any value of 1..T at any position; npos is not bounded by T, which is why this is not
@@ -1354,13 +1348,6 @@ __global__ void context_drop_kernel(const float* c, int B, int ncf, float p_drop
 // The draw: u = elements 3b, 3b + 1, 3b + 2 of the stream philox_uniform_kernel(out, 3 B, 0, 1, seed, sub, sub_dev)
 // writes; g = min(7, (int)(8 u0)), dy = min(H - 1, (int)(H u1)), dx = min(H - 1, (int)(H u2)) in fp32 (the min: u01 is
 // not promised to stay below 1).  mode bit 0 keeps g, bit 1 keeps dy and dx; the rest is 0, all three are consumed.
-static __device__ __forceinline__ float philox_u01_elem(unsigned long long seed, uint32_t sub, long long e) {
-    const long long q = e >> 2;
-    const U4 r = philox((uint32_t)q, (uint32_t)((unsigned long long)q >> 32), sub, 0x0417u, (uint32_t)seed,
-                        (uint32_t)(seed >> 32));
-    const int j = (int)(e & 3);
-    return u01(j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w)));
-}
 __global__ void augment_draw_kernel(int* ops, int B, int H, int mode, unsigned long long seed, uint32_t sub,
                                     const int* sub_dev) {
     if (sub_dev) sub += (uint32_t)*sub_dev;

@@ -1,6 +1,6 @@
 // The pieces the kernels that write the sampler state share (csrc/misc.hip: denoise, DDIM, DPM-Solver++, the blends;
-// csrc/guide.hip: the observation-guided step): the counter-based noise, the CFG combine, the per-run key and the
-// write-out.  The arithmetic of each update stays in its kernel.
+// csrc/guide.hip: the observation-guided step; csrc/flow.hip: the flow likelihood): the counter-based noise, the CFG
+// combine, the per-run key, the fp64 wave sum and the write-out.  The arithmetic of each update stays in its kernel.
 #pragma once
 #include "cdm_common.h"
 
@@ -37,6 +37,22 @@ static __device__ __forceinline__ float philox_normal(unsigned long long seed, u
     box_muller(v.x, v.y, z0, z1); box_muller(v.z, v.w, z2, z3);
     const int j = (int)(e & 3);
     return j == 0 ? z0 : (j == 1 ? z1 : (j == 2 ? z2 : z3));
+}
+
+// element e of the stream cdm_philox_uniform(out, n, 0, 1, seed, sub) writes (lo + (hi - lo) u01 is u01 itself there)
+static __device__ __forceinline__ float philox_u01_elem(unsigned long long seed, uint32_t sub, long long e) {
+    const long long q = e >> 2;
+    const U4 r = philox((uint32_t)q, (uint32_t)((unsigned long long)q >> 32), sub, 0x0417u, (uint32_t)seed,
+                        (uint32_t)(seed >> 32));
+    const int j = (int)(e & 3);
+    return u01(j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w)));
+}
+
+// fp64 sum over the 64 lanes of a wave, every lane gets it: a butterfly (xor 32, 16, ..., 1), the same bits every run
+static __device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
 
 // eps of a step: eu + w (ec - eu) when cfg (classifier-free guidance; model batch = 2n, cond half first), else eps[e].
@@ -77,6 +93,9 @@ static __device__ __forceinline__ float ddim_update(float xe, float ep, float a,
 // Key domain of a device z keyed by the position (a position program, where one timestep is visited more than once:
 // cdm_ddim_step_pos, cdm_ddim_step_guided).  The constant is the ASCII of "pos_step" and has no other meaning.
 constexpr unsigned long long STEP_NOISE_DOMAIN = 0x706F735F73746570ull;
+// Key domain of the Rademacher probes of the flow likelihood (csrc/flow.hip), keyed by the position.  The constant is
+// the ASCII of "flowprob" and has no other meaning.
+constexpr unsigned long long FLOW_PROBE_DOMAIN = 0x666C6F7770726F62ull;
 
 static inline int nblocks(long long total, int per = 256, int cap = 8192) {
     long long b = (total + per - 1) / per;

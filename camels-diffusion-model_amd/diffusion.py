@@ -43,6 +43,11 @@ Observation-guided sampling (not in the reference): ``DDPM.reconstruct`` draws m
 partly missing observation (``degrade`` makes one): :class:`GuidedDDIMSampler` follows every DDIM step with a step down
 the image gradient of the weighted misfit of the data prediction, one frozen forward and one full backward per position
 on the step graph (``cdm_obs_residual_grad``, ``cdm_ddim_step_guided``).
+
+Flow likelihood and DDIM encoding (not in the reference): ``DDPM.encode`` walks the sampler's timesteps upwards
+(:class:`DDIMEncoder`, :func:`encode_tables`) from a map to its latent; ``DDPM.log_likelihood`` is the log-density of the
+eta = 0 sampler by the change of variables along that walk (:class:`FlowLikelihood`: one frozen forward, one Rademacher
+probe and one full backward per position on the step graph; ``cdm_flow_probe``, ``cdm_flow_step``, ``cdm_flow_finish``).
 """
 from __future__ import annotations
 
@@ -393,6 +398,104 @@ def guided_tables(ab_t, taus):
     if not (np.isfinite(sq).all() and np.isfinite(ra).all()):
         raise ValueError("the schedule gives non-finite guidance tables (ab_t must lie in (0, 1] for t >= 1)")
     return (np.concatenate([[0.0], sq]).astype(np.float32), np.concatenate([[1.0], ra]).astype(np.float32))
+
+
+def encode_tables(ab_t, taus):
+    """Tables (from_t int32, ix fp32, ie fp32, g fp64) of the ascending (encoding) walk over ``taus``, S + 1 entries
+    indexed by the position p = S..1 in run order: position p performs the step k = S + 1 - p, from tau_{k-1} to tau_k,
+    with the network seeing the state at from_t[p] = tau_k (the usual DDIM-inversion convention: the walk visits the
+    sampler's timesteps and never t = 0).  With (cx_k, ce_k) the eta = 0 coefficients of :func:`ddim_tables` in fp64,
+
+        x <- ix x + ie eps        ix = 1 / cx_k,   ie = -ce_k / cx_k,   g = ie / ix = -ce_k
+
+    the inverse of the sampler's step at a fixed eps; the step's Jacobian is ix (I + g d eps / d x).  Entry 0 is the
+    identity (0, 1, 0, 0).  ``ab_t`` is the fp32 table of the Schedule; the arithmetic is fp64 numpy, ix and ie rounded
+    once to fp32, g kept in fp64 (the log-determinant is accumulated in fp64).  Pure host function.  Raises ValueError
+    for an invalid ``taus`` (:func:`timestep_subsequence`) and for a schedule that gives a non-finite entry."""
+    ab = _ab64(ab_t)
+    tau = timestep_subsequence(ab.size - 1, None, taus)
+    i = np.array(tau, dtype=np.int64)
+    j = np.array([0] + tau[:-1], dtype=np.int64)
+    ab_i, ab_j = ab[i], ab[j]
+    ab_j[0] = 1.0                                             # tau_0 = 0: ab_0 = 1 by definition
+    with np.errstate(divide="ignore", invalid="ignore"):     # a degenerate schedule is reported below
+        cx = np.sqrt(ab_j / ab_i)
+        ce = np.sqrt(1 - ab_j) - np.sqrt(ab_j * (1 - ab_i) / ab_i)
+        ix, ie, g = 1 / cx, -ce / cx, -ce
+    out = []
+    for v, v0, dt in ((ix, 1.0, np.float32), (ie, 0.0, np.float32), (g, 0.0, np.float64)):
+        if not np.isfinite(v).all() or not np.isfinite(v.astype(dt)).all():
+            raise ValueError("the schedule gives non-finite encoding coefficients (ab_t must lie in (0, 1) for t >= 1)")
+        out.append(np.concatenate([[v0], v[::-1]]).astype(dt))           # step k at the position S + 1 - k
+    from_t = np.array([0] + tau[::-1], dtype=np.int32)
+    return (from_t, *out)
+
+
+FLOW_FORMS = ("trace", "logdet")
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x: int) -> int:
+    z = (x + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def flow_run_key(seed: int, r: int) -> int:
+    """The 64-bit run key of probe run ``r`` under ``seed``: splitmix64(splitmix64(seed) + r mod 2^64) (Steele et al.
+    2014, the finaliser of java.util.SplittableRandom).  splitmix64 is a bijection, so two pairs (seed, r) share a key
+    only if splitmix64(seed) - splitmix64(seed') = r' - r: neighbouring seeds do not share probes, and results pooled
+    over seeds are as independent as results over r.  Pure host function."""
+    return _splitmix64((_splitmix64(int(seed) & _M64) + int(r)) & _M64)
+
+
+def check_flow(maps, params, n_cfeat: int, H: int, in_channels: int = 1, guide_w: float = 0.0, form: str = "logdet",
+               n_probe: int = 1, max_rows: int = 32):
+    """Validate the inputs of ``DDPM.log_likelihood`` -> (maps [n,1,H,H], params [n,n_cfeat] or None) as given (any
+    device); ``maps`` may come without the channel axis.  Pure host function.  ValueError, before anything is allocated
+    or drawn: ``guide_w`` != 0 (the density is that of the unguided sampler: the CFG combination of two networks has
+    its own Jacobian, which is not built); a model with in_channels > 1; ``form`` not "logdet" or "trace"; ``n_probe``
+    or ``max_rows`` not an integer >= 1; maps not [n,1,H,H] / [n,H,H] with n >= 1, not floating point or non-finite;
+    params not [n, n_cfeat], not floating point or non-finite."""
+    if isinstance(guide_w, bool) or not float(guide_w) == 0.0:
+        raise ValueError(f"log_likelihood is the density of the unguided sampler: guide_w must be 0, got {guide_w!r}")
+    if in_channels != 1:
+        raise ValueError(f"log_likelihood is single-channel, like the samplers: the model has in_channels = {in_channels}")
+    if form not in FLOW_FORMS:
+        raise ValueError(f"form must be one of {FLOW_FORMS}, got {form!r}")
+    _posint("n_probe", n_probe)
+    _posint("max_rows", max_rows)
+    x = torch.as_tensor(maps)
+    if x.dim() == 3:
+        x = x[:, None]
+    if x.dim() != 4 or tuple(x.shape[1:]) != (1, H, H) or x.shape[0] < 1:
+        raise ValueError(f"maps must have shape [n, 1, {H}, {H}] or [n, {H}, {H}], got {tuple(torch.as_tensor(maps).shape)}")
+    if not x.is_floating_point() or not bool(torch.isfinite(x).all()):
+        raise ValueError("maps must be a finite floating-point array")
+    if params is not None:
+        params = torch.as_tensor(params)
+        if tuple(params.shape) != (x.shape[0], n_cfeat):
+            raise ValueError(f"params must have shape {(x.shape[0], n_cfeat)}, got {tuple(params.shape)}")
+        if not params.is_floating_point() or not bool(torch.isfinite(params).all()):
+            raise ValueError("params must be a finite floating-point array")
+    return x, params
+
+
+class FlowResult(NamedTuple):
+    """What ``DDPM.log_likelihood`` returns: host tensors, fp64 unless noted.  ``logp`` is the log-density, per map, of
+    the eta = 0 sampler's model at guide_w = 0, in the sampler's noise convention, discretised at S positions, with a
+    stochastic trace estimate.  It is not a bound, and the reference does not compute it."""
+    logp: torch.Tensor          # [n]: the mean over the probes
+    logp_probe: torch.Tensor    # [R, n]: one value per probe run
+    stderr: torch.Tensor        # [n]: the standard error of that mean over the probes; NaN for R = 1
+    bpd: torch.Tensor           # [n]: -logp / (D ln 2) on the model's own data scale, no dequantisation offset
+    latent: torch.Tensor        # [n, 1, H, H] fp32: the encoded x_T (the same for every probe)
+    prior: torch.Tensor         # [n]: log N(x_T; 0, I)
+    logdet: torch.Tensor        # [n]: (D / 2) log ab_T + sum_k ld_k, the mean over the probes
+    trace_hist: torch.Tensor    # [R, S, n]: q_k = v^T J_k v in step order k = 1..S
+    invalid: torch.Tensor       # [n] bool: a non-finite ld_k in any probe run (logp is then NaN)
+    taus: list                  # the timesteps tau_1 < ... < tau_S = T of the walk
 
 
 class Program(NamedTuple):
@@ -1138,6 +1241,144 @@ class GuidedDDIMSampler(_StridedSampler):
         return x, inter, L.sqrt().cpu()
 
 
+class DDIMEncoder(_StridedSampler):
+    """DDIM inversion: the ascending walk of :func:`encode_tables` from a map x_0 to its latent x_T on the eval forward
+    (no backward), on GraphSampler's buffers, snapshots and captured step graph.  Not in the reference.
+
+    At the position p = S..1 the prologue hands the network the timestep from_t[p] = tau_{S+1-p} and the unchanged
+    ``cdm_ddim_step_pos`` applies x <- ix[p] x + ie[p] eps with the tables (ix, ie, 0): the encoder needs no kernel of
+    its own.  CFG (``guide_w`` > 0 with params) combines eps as the samplers do.  Nothing is random but the shortcut
+    row(s) of every forward, drawn from the CPU RNG for p = S..1, cond before uncond (``prepare_rng``); decoding with
+    ``sample_ddim_from_noise(eta=0)`` draws its own, so a round trip is exact only up to those and the discretisation.
+    Snapshots: ``snapshot_slots(S, save_rate)`` on positions, the last one the latent."""
+
+    def __init__(self, model, sched: Schedule, n: int, guide_w: float, params: Optional[torch.Tensor], steps=50,
+                 spacing="uniform", save_rate: int = 20, steps_per_graph: int = 10, seed: int = 1234,
+                 snapshots: bool = True, use_graph: bool = True):
+        taus = timestep_subsequence(sched.T, steps, spacing)
+        tables = encode_tables(sched.ab_t, taus)              # validates before anything is allocated
+        if model.in_channels != 1:
+            raise ValueError(f"encoding is single-channel, like the samplers: the model has in_channels = "
+                             f"{model.in_channels}")
+        super().__init__(model, sched, n, guide_w, params, taus, save_rate, "device", steps_per_graph, seed, snapshots,
+                         use_graph, None, None, None)
+        self.K = min(self.K, self.npos)                      # a short walk is one graph
+        self.steps_t, self.ix, self.ie = (torch.from_numpy(v).to(self.dev) for v in tables[:3])
+        self.sigma0 = torch.zeros(self.npos + 1, device=self.dev)
+
+    def _draws_host_z(self, p):
+        return False
+
+    def _update(self, s, eps, numel):
+        lib().cdm_ddim_step_pos(_p(self.xbuf), _p(self.xbuf), _p(self.xbuf) if self.cfg else None, numel, _p(eps),
+                                1 if self.cfg else 0, self.guide_w, _p(self.cur_k), _p(self.ix), _p(self.ie),
+                                _p(self.sigma0), self.npos, None, numel, self.seed, _p(self.zseed), _p(self.slot),
+                                _p(self.snaps), s)
+
+
+class FlowLikelihood(_StridedSampler):
+    """The log-density of the eta = 0 DDIM sampler's model by the change of variables along the probability-flow ODE
+    (Song et al. 2021, §4.3 and App. D.2; not in the reference; DESIGN §1 has the definition).
+
+    At the position p = S..1 of the ascending walk (:func:`encode_tables`), all on the captured step graph and with
+    nothing read back between positions:
+        eps  = the frozen train-structured forward at the timestep from_t[p] (model.eval()'s forward kept for a backward)
+        v    = the Rademacher probe of the position, written into deps                         (``cdm_flow_probe``)
+        dx   = J^T v, the engine's full backward with ``dx=``
+        q    = <dx, v>;  acc += ld(g[p] q);  x <- ix[p] x + ie[p] eps                         (``cdm_flow_step``)
+    and after the walk ``cdm_flow_finish`` adds log N(x_T; 0, I) + (D / 2) log ab_T.  ``form``: "trace", ld = g q, or
+    "logdet", ld = D log1p(g q / D).  The probe is keyed by position and element, not by the row: all maps of a run
+    share their probes (the scan's common random numbers).  ``run(x_0, n_probe=R, seed=)`` replays the same graph R
+    times with the run keys :func:`flow_run_key` (seed, r), r = 0..R-1, handed to the kernels through a device value, so
+    one sampler and one captured graph serve every seed; the shortcut rows are whatever ``prepare_rng`` drew last and
+    stay the same for every probe run, so all probes see one function.
+
+    Like :class:`GuidedDDIMSampler` it runs on the engine's train pack and a frozen workspace (fp32 activations of all
+    n rows: n is bounded by memory), renews the pack token and invalidates the model's eval pack.  The parameter
+    gradients the backward also computes go to scratch and are wasted work.  ValueError before anything is allocated:
+    ``guide_w`` != 0, in_channels > 1, an unknown ``form``, what :func:`encode_tables` raises."""
+
+    def __init__(self, model, sched: Schedule, n: int, params: Optional[torch.Tensor], steps=50, spacing="uniform",
+                 form: str = "logdet", steps_per_graph: int = 10, seed: int = 1234, use_graph: bool = True,
+                 guide_w: float = 0.0):
+        taus = timestep_subsequence(sched.T, steps, spacing)
+        tables = encode_tables(sched.ab_t, taus)              # validates before anything is allocated
+        if not float(guide_w) == 0.0:
+            raise ValueError(f"the flow likelihood is the unguided sampler's density: guide_w must be 0, got {guide_w!r}")
+        if model.in_channels != 1:
+            raise ValueError(f"the flow likelihood is single-channel: the model has in_channels = {model.in_channels}")
+        if form not in FLOW_FORMS:
+            raise ValueError(f"form must be one of {FLOW_FORMS}, got {form!r}")
+        self.form, self.run_seed = form, int(seed)
+        # the kernels' by-value seed is 0: the whole run key travels in zseed
+        super().__init__(model, sched, n, 0.0, params, taus, 20, "device", steps_per_graph, 0, False, use_graph, None,
+                         None, None)
+        dev, H = self.dev, self.H
+        self.K = min(self.K, self.npos)                      # a short walk is one graph
+        self.steps_t, self.ix, self.ie, self.g = (torch.from_numpy(v).to(dev) for v in tables)
+        self.log_abT = float(np.log(_ab64(sched.ab_t)[sched.T]))
+        self.deps, self.dx = torch.empty(n, H, H, device=dev), torch.empty(n, H, H, device=dev)
+        F64 = lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=dev)    # noqa: E731
+        self.acc, self.prior, self.logp, self.hist = F64(n), F64(n), F64(n), F64(self.npos + 1, n)
+        self.invalid = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._rehome(self.P)
+
+    def _repack(self):
+        self.eng.repack(self.P, True, _s())
+        self.eng.train_pack_token = object()
+        self.model._invalidate_eval_pack()
+
+    def _workspace(self):
+        return self.eng.workspace(self.B, True, frozen=True)
+
+    def _rehome(self, P):
+        super()._rehome(P)
+        self.G = {k: torch.empty_like(P[k]) for k in self.model._param_names}   # scratch: written, never read
+
+    def _draws_host_z(self, p):
+        return False
+
+    def _step(self, s):
+        self._prologue(s)
+        nf = self.model.n_feat
+        eps = self.eng.forward(self.ws, self.P, self.xbuf, self.t_cur, self.cbuf, self.sc_cur[:nf], self.sc_cur[nf:],
+                               self.n, s, frozen=True)
+        lb = lib()
+        lb.cdm_flow_probe(_p(self.deps), self.n, self.H, _p(self.cur_k), self.npos, 0, _p(self.zseed), s)
+        self.eng.backward(self.ws, self.P, self.deps, self.G, s, dx=self.dx)
+        lb.cdm_flow_step(_p(self.xbuf), _p(eps), _p(self.dx), self.n, self.H, _p(self.cur_k), _p(self.ix), _p(self.ie),
+                         _p(self.g), self.npos, FLOW_FORMS.index(self.form), 0, _p(self.zseed), _p(self.acc),
+                         _p(self.hist), _p(self.invalid), s)
+
+    def run(self, x_0: torch.Tensor, n_probe: int = 1, steps: Optional[int] = None, seed: Optional[int] = None):
+        """``n_probe`` runs of the walk (or of its first ``steps`` positions) from the maps x_0 [n,1,H,H], run r under
+        the key flow_run_key(seed, r) (``seed`` None: the constructor's) -> dict of host tensors: logp [R, n], prior
+        [R, n], acc [R, n] (sum_k ld_k), hist [R, S, n] (q_k in step order), invalid [n] bool, latent [n,1,H,H] fp32."""
+        n, H = self.n, self.H
+        R = _posint("n_probe", n_probe)
+        seed = self.run_seed if seed is None else int(seed)
+        self.prepare()
+        total = self.npos if steps is None else min(int(steps), self.npos)
+        x0 = x_0.to(self.dev, torch.float32).reshape(n, H, H)
+        self.invalid.zero_()
+        out = dict(logp=[], prior=[], acc=[], hist=[])
+        for r in range(R):
+            key = flow_run_key(seed, r)
+            self.zseed.fill_(key - (1 << 64) if key >> 63 else key)      # the same 64 bits as a signed value
+            self.acc.zero_(); self.hist.zero_()
+            self.xbuf.copy_(x0)
+            self.ctr.fill_(self.npos)
+            _run_steps(self.graph, self._step, self.K, total)
+            lib().cdm_flow_finish(_p(self.xbuf), n, H, self.log_abT, _p(self.acc), _p(self.prior), _p(self.logp), _s())
+            out["logp"].append(self.logp.cpu()); out["prior"].append(self.prior.cpu()); out["acc"].append(self.acc.cpu())
+            out["hist"].append(self.hist[1:].flip(0).cpu())
+        res = {k: torch.stack(v) for k, v in out.items()}
+        res["invalid"] = self.invalid.cpu() != 0
+        res["latent"] = self.xbuf.reshape(n, 1, H, H).cpu()
+        res["log_abT"] = self.log_abT
+        return res
+
+
 PLAIN = (1, 1, None)          # (resample, jump, t_start) of the plain walk: no position program
 
 
@@ -1387,6 +1628,86 @@ class DDPM:
         smp.prepare_rng(host_z=zs == "host")
         return smp.run(x_T, obs=obs_t, weight=wgt)
 
+    @torch.no_grad()
+    def encode(self, maps, params=None, guide_w=0.0, steps=50, spacing="uniform", save_rate=20):
+        """DDIM inversion (:class:`DDIMEncoder`): the maps [n,1,H,H] (or [n,H,H]) to their latents x_T along the
+        ascending walk over ``steps`` of the T timesteps (``spacing`` as :meth:`sample_ddim`) -> (x_T [n,1,H,H] on the
+        device, intermediate np [slots,n,1,H,H] by ``snapshot_slots(steps, save_rate)``).  ``params`` [n, n_cfeat] or None;
+        CFG when ``guide_w`` > 0.  Encoding under params c and decoding with ``sample_ddim_from_noise(x_T, c', eta=0)``
+        over the same timesteps asks what the field would look like under c'.  The shortcut rows are drawn from the CPU
+        RNG; nothing else is random.  Encoders are cached per configuration.  ValueError, before anything is drawn or
+        allocated: maps of another shape or non-finite, params not [n, n_cfeat], a model with in_channels > 1, what
+        :func:`encode_tables` raises."""
+        H = self.model.h
+        if self.model.in_channels != 1:
+            raise ValueError("encoding is single-channel, like the samplers: the model has in_channels = "
+                             f"{self.model.in_channels}")
+        x, params = check_flow(maps, params, self.n_cfeat, H)
+        if isinstance(guide_w, bool) or not np.isfinite(guide_w):
+            raise ValueError(f"guide_w must be finite, got {guide_w!r}")
+        n = x.shape[0]
+        encode_tables(self.sched.ab_t, timestep_subsequence(self.T, steps, spacing))
+        key = ("encode", n, float(guide_w) if params is not None else 0.0, params is not None, save_rate, steps,
+               spacing if isinstance(spacing, str) else tuple(spacing))
+        smp = self._samplers.get(key)
+        if smp is None:
+            smp = self._samplers[key] = DDIMEncoder(self.model, self.sched, n, guide_w, params, steps, spacing, save_rate,
+                                                    seed=self.seed)
+        elif params is not None:
+            smp.cbuf[:n] = params.to(smp.dev, torch.float32).reshape(n, -1)
+        smp.prepare_rng(host_z=False)
+        return smp.run(x)
+
+    @torch.no_grad()
+    def log_likelihood(self, maps, params=None, steps=50, spacing="uniform", n_probe=1, form="logdet", seed=None,
+                       max_rows=32, guide_w=0.0) -> FlowResult:
+        """log p(x | c) of the maps [n,1,H,H] (or [n,H,H]) under ``params`` [n, n_cfeat] (None: no context) ->
+        :class:`FlowResult`.  It is the log-density, per map, of the eta = 0 sampler's model at guide_w = 0, in the
+        sampler's noise convention.  It is discretised at S = ``steps`` positions, with a stochastic trace estimate.  It
+        is not a bound, and the reference does not compute it.  :class:`FlowLikelihood` has the walk; ``form``: "logdet"
+        (default; exact where the network's Jacobian is a multiple of the identity) or "trace" (the textbook Euler step,
+        first order in 1 / S).
+
+        ``n_probe`` = R probe runs with the keys :func:`flow_run_key` (seed, r) (``seed`` None: this object's; the keys
+        of different seeds do not overlap, so results may be pooled over seeds) give ``logp_probe`` [R, n], their mean
+        ``logp`` and its standard error.  One sampler per chunk size serves every seed.  All maps share their probes, and the shortcut rows, drawn from the
+        CPU RNG once per call, are the same for every map, probe and chunk.  The maps go in chunks of ``max_rows`` (the
+        frozen workspace keeps the activations of every row of a chunk).  Cost: R * S forward + full-backward pairs per
+        chunk.  ValueError, before anything is drawn or allocated: what :func:`check_flow` and :func:`encode_tables`
+        list."""
+        H = self.model.h
+        x, params = check_flow(maps, params, self.n_cfeat, H, self.model.in_channels, guide_w, form, n_probe, max_rows)
+        seed = self.seed if seed is None else seed
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 63:
+            raise ValueError(f"seed must be an integer in [0, 2^63), got {seed!r}")
+        taus = timestep_subsequence(self.T, steps, spacing)
+        encode_tables(self.sched.ab_t, taus)
+        n, D = x.shape[0], H * H
+        parts, rows = [], None
+        for lo in range(0, n, int(max_rows)):
+            m = min(int(max_rows), n - lo)
+            c = None if params is None else params[lo:lo + m]
+            key = ("flow", m, params is not None, steps, spacing if isinstance(spacing, str) else tuple(spacing), form)
+            smp = self._samplers.get(key)
+            if smp is None:
+                smp = self._samplers[key] = FlowLikelihood(self.model, self.sched, m, c, steps, spacing, form)
+            elif c is not None:
+                smp.cbuf[:m] = c.to(smp.dev, torch.float32).reshape(m, -1)
+            if rows is None:
+                smp.prepare_rng(host_z=False)
+                rows = smp.sc_table.clone()
+            else:
+                smp.sc_table.copy_(rows)
+            parts.append(smp.run(x[lo:lo + m], n_probe, seed=int(seed)))
+        cat = lambda k, d: torch.cat([p[k] for p in parts], dim=d)      # noqa: E731
+        logp_probe, prior, acc, hist = cat("logp", 1), cat("prior", 1), cat("acc", 1), cat("hist", 2)
+        R = logp_probe.shape[0]
+        logp = logp_probe.mean(0)
+        stderr = logp_probe.std(0, unbiased=True) / np.sqrt(R) if R > 1 else torch.full_like(logp, float("nan"))
+        logdet = (0.5 * D * parts[0]["log_abT"] + acc).mean(0)
+        return FlowResult(logp, logp_probe, stderr, -logp / (D * np.log(2.0)), cat("latent", 0), prior[0], logdet, hist,
+                          cat("invalid", 0), list(taus))
+
     def param_scan(self, maps, candidates, **kwargs):
         """:func:`cdm_amd.param_scan` of this model under this schedule: ``score[m, k]`` of every map under every
         candidate parameter vector (lower = preferred) -> ScanResult.  ``kwargs``: t_grid, n_steps, n_noise, weight, seed,
@@ -1425,3 +1746,26 @@ def sample_ddpm(model, n_sample=1, size=64, device=None, params=None, guide_w=0.
             raise ValueError(f"solver must be 'ddim' or 'dpmpp', got {solver!r}")
         return d.sample_ddim(n_sample, size, device, params, guide_w, steps, eta, spacing, **ipk)[0]
     return d.sample_ddpm(n_sample, size, device, params, guide_w, **ipk)[0]
+
+
+def _ddpm_of(model, timesteps, device, b_t, a_t, ab_t, **kw):
+    given = [v is not None for v in (b_t, a_t, ab_t)]
+    if any(given) and not all(given):
+        raise ValueError("pass all of b_t, a_t, ab_t or none of them")
+    return DDPM(model, timesteps, device or model.out[3].weight.device,
+                sched_tensors=(b_t, a_t, ab_t) if all(given) else None, **kw)
+
+
+def encode(model, maps, timesteps, params=None, guide_w=0.0, b_t=None, a_t=None, ab_t=None, device=None, *, steps=50,
+           spacing="uniform", save_rate=20):
+    """Functional form of :meth:`DDPM.encode` on a caller's schedule, as :func:`sample_ddpm` takes one (b_t / a_t / ab_t:
+    all three or none; None builds the default schedule of ``timesteps``) -> (x_T, intermediate)."""
+    return _ddpm_of(model, timesteps, device, b_t, a_t, ab_t).encode(maps, params, guide_w, steps, spacing, save_rate)
+
+
+def log_likelihood(model, maps, params, timesteps, b_t=None, a_t=None, ab_t=None, device=None, *, steps=50,
+                   spacing="uniform", n_probe=1, form="logdet", seed=1234, max_rows=32) -> FlowResult:
+    """Functional form of :meth:`DDPM.log_likelihood` on a caller's schedule (b_t / a_t / ab_t: all three or none; None
+    builds the default schedule of ``timesteps``) -> :class:`FlowResult`."""
+    return _ddpm_of(model, timesteps, device, b_t, a_t, ab_t).log_likelihood(maps, params, steps, spacing, n_probe, form,
+                                                                            seed, max_rows)

@@ -362,6 +362,22 @@ class ScanResult(_Result):
         super().__init__(score, t_grid, n_noise, weight)
         self.candidates = candidates
 
+    @classmethod
+    def from_logp(cls, logp, candidates) -> "ScanResult":
+        """A result whose score is ``-logp`` [M, K] (fp64), ``logp[m, k]`` the log-density of map m under candidate k
+        as ``DDPM.log_likelihood`` gives it (one call per candidate, the same ``seed`` so the probes are shared).
+        This is the case where ``scale = 1`` means something: ``log_weights(1)`` is then log p up to a constant per
+        map and ``posterior(1)`` the posterior under a flat prior over the candidates, of the discretised,
+        probe-estimated density that log_likelihood documents.  ``t_grid`` is empty and ``weight`` is "logp".
+        ValueError: logp not [M, K], candidates not [K, ncf], or a NaN in logp (an invalid row has no density)."""
+        lp = torch.as_tensor(logp).detach().to(torch.float64)
+        c = torch.as_tensor(candidates).detach().to("cpu", torch.float32)
+        if lp.dim() != 2 or c.dim() != 2 or lp.shape[1] != c.shape[0] or lp.shape[0] < 1 or c.shape[0] < 1:
+            raise ValueError(f"logp must be [M, K] and candidates [K, ncf], got {tuple(lp.shape)} and {tuple(c.shape)}")
+        if bool(torch.isnan(lp).any()):
+            raise ValueError("logp holds a NaN: an invalid row has no density to weigh")
+        return cls(-lp, c, [], 1, "logp")
+
     def log_weights(self, scale) -> torch.Tensor:
         """-scale (score - min_k score) [M, K]: 0 at each map's best candidate."""
         s = self.score

@@ -25,6 +25,13 @@ to train on synthetic maps of the same shape.
 Plots of the reference (loss curves, PDFs, P(k)) are analysis, outside the hot path: losses, samples and
 timings are written as .npy / .log instead.
 
+After the sampling (off by default; the shortcut rows of both come from the CPU RNG re-seeded with --seed):
+  --encode-maps PATH.npy [--encode-params PATH.npy]
+                 DDIM inversion of the maps (DDPM.encode, --loglik-steps positions) -> latents.npy
+  --loglik-maps PATH.npy --loglik-params PATH.npy [--loglik-steps S --loglik-probes R --loglik-form logdet|trace]
+                 the flow log-likelihood of the maps (DDPM.log_likelihood: the eta = 0 sampler's log-density, discretised
+                 at S positions with R Rademacher probes; not a bound) -> log_likelihood.npz: logp, stderr, bpd, invalid, taus
+
 Training for guided sampling (all off by default; without them the outputs are those described above):
   --p-uncond P   each sample's context is replaced by the null condition c = 0 with probability P in a step, so the
                  c = 0 forward of classifier-free guidance (--guide-w > 0) is one the model was trained on.
@@ -222,7 +229,40 @@ def main(argv=None):
     ap.add_argument("--fit-noise", type=int, default=1, metavar="R", help="noise draws per fitted timestep")
     ap.add_argument("--fit-weight", choices=["uniform", "nll"], default="uniform",
                     help="per-timestep weight of the fit's squared error: 1, or 1 / (2 b_t)")
+    ap.add_argument("--encode-maps", default=None, metavar="PATH.npy",
+                    help="maps [n,H,W] or [n,1,H,W] (normalised data units) to encode to their DDIM latents (latents.npy)")
+    ap.add_argument("--encode-params", default=None, metavar="PATH.npy",
+                    help="parameters [n,NUM_PARAMS] of --encode-maps (default: no context)")
+    ap.add_argument("--loglik-maps", default=None, metavar="PATH.npy",
+                    help="maps [n,H,W] or [n,1,H,W] (normalised data units) whose flow log-likelihood is computed "
+                         "(log_likelihood.npz)")
+    ap.add_argument("--loglik-params", default=None, metavar="PATH.npy", help="parameters [n,NUM_PARAMS] of --loglik-maps")
+    ap.add_argument("--loglik-steps", type=int, default=None, metavar="S",
+                    help="positions of the likelihood walk, also of --encode-maps (default min(50, TIMESTEPS))")
+    ap.add_argument("--loglik-probes", type=int, default=1, metavar="R", help="Rademacher probe runs")
+    ap.add_argument("--loglik-form", choices=["logdet", "trace"], default="logdet",
+                    help="per-step log-determinant: D log1p(g q / D), or the first-order g q")
     a = ap.parse_args(argv)
+    a.flow_steps = min(50, a.timesteps) if a.loglik_steps is None else a.loglik_steps
+    a.encode = a.loglik = None
+    if a.encode_maps is None and a.encode_params is not None:
+        ap.error("--encode-params needs --encode-maps")
+    if (a.loglik_maps is None) != (a.loglik_params is None):
+        ap.error("--loglik-maps and --loglik-params go together")
+    for name, mp, pp in (("encode", a.encode_maps, a.encode_params), ("loglik", a.loglik_maps, a.loglik_params)):
+        if mp is None:
+            continue
+        if a.num_params is None and pp is not None:
+            ap.error(f"--{name}-params needs a conditioned run (NUM_PARAMS)")
+        try:
+            from cdm_amd.diffusion import check_flow, encode_tables, timestep_subsequence, Schedule
+            fm = torch.from_numpy(np.load(mp, allow_pickle=False))
+            fp = None if pp is None else torch.from_numpy(np.load(pp, allow_pickle=False))
+            fm, fp = check_flow(fm, fp, a.num_params or 0, a.height, form=a.loglik_form, n_probe=a.loglik_probes)
+            encode_tables(Schedule(a.timesteps, "cpu").ab_t, timestep_subsequence(a.timesteps, a.flow_steps, a.spacing))
+            setattr(a, name, (fm.float(), None if fp is None else fp.float()))
+        except (OSError, ValueError) as e:
+            ap.error(f"--{name}-maps / --{name}-params: {e}")
     if (a.scan_maps is None) != (a.scan_candidates is None):
         ap.error("--scan-maps and --scan-candidates go together")
     a.scan = None
@@ -563,6 +603,24 @@ def sample_and_compare(a, model, maps_d, params_d, test_idx, n_total, conditiona
                  t_grid=np.asarray(fr.t_grid, dtype=np.int64), best=fr.best().cpu().numpy())
         log.write(f"Parameter fit of {fscore.shape[0]} maps from {fscore.shape[1]} starts, {a.fit_iters} iterations, "
                   f"{len(ftg)} timesteps x {a.fit_noise} noise draws, weight={a.fit_weight}: {dt:.2f} s\n")
+    # the shortcut rows of the two walks below come from the CPU RNG: seeded here, so the files can be reproduced from
+    # the checkpoint with DDPM.encode / DDPM.log_likelihood after torch.manual_seed(SEED)
+    if a.encode is not None:
+        emaps, eparams = a.encode
+        torch.manual_seed(a.seed)
+        latents, _ = d.encode(emaps, eparams, steps=a.flow_steps, spacing=a.spacing)
+        np.save(os.path.join(out_dir, "latents.npy"), latents.cpu().numpy())
+        log.write(f"DDIM encoding of {emaps.shape[0]} maps, {a.flow_steps} positions\n")
+    if a.loglik is not None:
+        lmaps, lparams = a.loglik
+        torch.manual_seed(a.seed)
+        fl = d.log_likelihood(lmaps, lparams, steps=a.flow_steps, spacing=a.spacing, n_probe=a.loglik_probes,
+                              form=a.loglik_form)
+        np.savez(os.path.join(out_dir, "log_likelihood.npz"), logp=fl.logp.numpy(), stderr=fl.stderr.numpy(),
+                 bpd=fl.bpd.numpy(), invalid=fl.invalid.numpy(), taus=np.asarray(fl.taus, dtype=np.int64))
+        log.write(f"Flow log-likelihood of {lmaps.shape[0]} maps, {a.flow_steps} positions x {a.loglik_probes} probes, "
+                  f"form={a.loglik_form}: {a.loglik_probes * a.flow_steps} forward + backward pairs per chunk, "
+                  f"{int(fl.invalid.sum())} invalid\n")
     with open(os.path.join(out_dir, "means.txt"), "w") as f:
         f.write(f"Processed Images Mean: {x.mean().item()}\nReconstructed Images Mean: {rec.mean().item()}\n")
 

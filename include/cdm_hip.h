@@ -580,6 +580,39 @@ int cdm_ddim_step_guided(const float* xin, float* x, float* x2, long long numel,
                          const float* z_table, long long zstride, unsigned long long seed, const long long* seed_dev,
                          const int* snap_slot, float* snaps, const float* grad_dir, const float* dx, const double* L,
                          float zeta, int H, void* stream);
+/* Flow likelihood (diffusion.FlowLikelihood, not in the reference; csrc/flow.hip): the log-density of the eta = 0 DDIM
+ * sampler's model by the change of variables along the ascending (encoding) walk x -> ix[p] x + ie[p] eps(x), whose
+ * Jacobian is ix[p] (I + g[p] J), J = d eps / d x.  A step is cdm_sample_prologue_sub (steps = the ascending timesteps
+ * by position), the frozen train-structured forward, cdm_flow_probe into deps, the engine's full backward with dx
+ * (dx = J^T v), and cdm_flow_step.  No kernel synchronises or allocates; the position p = *cur_k is read from the device
+ * and a p outside 1..npos writes nothing.  No timing of these kernels has been taken.
+ * cdm_flow_probe: the Rademacher probe v [n][H][H], v[b][e] = u[e] < 0.5f ? 1 : -1 with u what
+ * cdm_philox_uniform(out, H H, 0, 1, key, sub = p) writes, key = (seed ^ *seed_dev) ^ a fixed constant of its own
+ * (seed_dev optional).  Keyed by the position and the element within the map, not by the row: all rows of a run share
+ * their probes (common random numbers), two run keys give different ones.  hipErrorInvalidValue, nothing launched: v or
+ * cur_k null; n, H or npos < 1.
+ * cdm_flow_step, one block of 256 threads per row, v regenerated from the same key (the buffer the backward was handed
+ * is not read), ix / ie fp32 and g fp64 tables [npos + 1] by position (diffusion.encode_tables), D = H H:
+ *   q       = sum_e (double)dx[e] (double)v[e]     fp64: thread t adds e = t, t + 256, ... ascending, a wave64 butterfly,
+ *                                                  then (w0 + w1) + (w2 + w3) through LDS: the same bits every run
+ *   form 0 (trace):   ld = g[p] q
+ *   form 1 (logdet):  a = (g[p] q) / D;  ld = D log1p(a) where a > -1, else NaN
+ *   acc[row] += ld;   hist[p n + row] = q  (hist [npos + 1][n]);   invalid[row] = 1 where ld is not finite
+ *   x[e] <- ix[p] x[e] + ie[p] eps[e]              fp32: two products and one sum, each one rounding
+ * Every fp64 line is one rounding too; log1p is evaluated from IEEE operations alone (frexp, an atanh series of twelve
+ * terms by Horner; the kernel's comment has every line), so a host restatement reproduces acc bit for bit.  x, eps, dx
+ * [n][H][H]; there is no CFG form.  hipErrorInvalidValue, nothing launched: a pointer null; n, H or npos < 1; form not
+ * 0 or 1.
+ * cdm_flow_finish, per row, the same summation order: ss = sum_e (double)x[e]^2; prior[row] = -0.5 ss - (0.5 D) log(2 pi)
+ * (log N(x_T; 0, I)); logp[row] = (prior[row] + (0.5 D) log_abT) + acc[row].  hipErrorInvalidValue, nothing launched: a
+ * pointer null; n or H < 1; log_abT not finite or > 0. */
+int cdm_flow_probe(float* v, int n, int H, const int* cur_k, int npos, unsigned long long seed, const long long* seed_dev,
+                   void* stream);
+int cdm_flow_step(float* x, const float* eps, const float* dx, int n, int H, const int* cur_k, const float* ix,
+                  const float* ie, const double* g, int npos, int form, unsigned long long seed,
+                  const long long* seed_dev, double* acc, double* hist, int* invalid, void* stream);
+int cdm_flow_finish(const float* x, int n, int H, double log_abT, const double* acc, double* prior, double* logp,
+                    void* stream);
 /* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
  * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
  * step draws fresh numbers on every replay). */
