@@ -1,6 +1,10 @@
 """Op-level parity of the HIP contraction kernels against plain torch fp32 on CPU (GPU box only).
 
 Tolerance: fp32 MFMA vs CPU fp32 with different summation order -> |err| <= 2e-5 * max|ref| + 1e-5.
+
+The fused forms of the LDS-halo conv and of the kernel-row weight gradient (BN-ReLU / BN-backward staging, accumulate and
+relu epilogues, statistics and max / min keys, the eval epilogues, bf16 storage, shapes off the workload's) are held to
+fp64 references, bit for bit on exact data, in tests/test_gpu_halo_ops.py.
 """
 import os
 
