@@ -42,19 +42,3 @@ CDM_API int cdm_conv3x3_dgrad_x16_bnbwd_dy(const float* g, int ldg, const float*
         default: return run(float{}, float{});
     }
 }
-CDM_API int cdm_conv3x3_dgrad_x16_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s,
-                                        const float* t, const float* mean, const float* invstd, const float* A,
-                                        const float* B, const float* Cc, int N, int H, int W, int C, const void* wx,
-                                        const float* amax_dy, const float* amax_w, float* out, int ldo, int Cout,
-                                        int flags, float* amax_out, int nterm, int dt, void* stream) {
-    return cdm_conv3x3_dgrad_x16_bnbwd_dy(g, ldg, y, ldy, s, t, mean, invstd, A, B, Cc, N, H, W, C, wx, amax_dy, amax_w,
-                                          out, ldo, Cout, flags, amax_out, nullptr, nterm, dt, stream);
-}
-CDM_API int cdm_conv3x3_dgrad_h3_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s,
-                                       const float* t, const float* mean, const float* invstd, const float* A,
-                                       const float* B, const float* Cc, int N, int H, int W, int C, const void* wx,
-                                       const float* amax_dy, const float* amax_w, float* out, int ldo, int Cout,
-                                       int flags, float* amax_out, void* stream) {
-    return cdm_conv3x3_dgrad_x16_bnbwd(g, ldg, y, ldy, s, t, mean, invstd, A, B, Cc, N, H, W, C, wx, amax_dy, amax_w,
-                                       out, ldo, Cout, flags, amax_out, NT_H3, 0, stream);
-}

@@ -637,8 +637,9 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_f32_kernel(LA la, LB lb, EP 
     ep(acc, m0 + wm * 64, n0 + wn * 64, lane, wm, wn, smem, tid);
 }
 
-template <class LA, class LB, class EP, bool A_MCONTIG, int BK = 16, bool XCD_REMAP = false>
+template <class LA, class LB, class EP, bool A_MCONTIG, bool XCD_REMAP = false>
 static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, int K, int splits, hipStream_t s) {
+    constexpr int BK = 16;   // the one K step every caller uses
     const int ktiles = (K + BK - 1) / BK;
     if (splits < 1) splits = 1;
     if (splits > ktiles) splits = ktiles > 0 ? ktiles : 1;
@@ -1691,42 +1692,40 @@ __global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* 
     }
 }
 
-// ============================== conv3x3 weight gradient, split-bf16, transposed LDS reads ==============================
-// dW[co][tap*Cin + ci] (per split-K slab) = sum_pix dY[pix][co] * X[pix shifted by tap][ci]; K = pixels.
+// ============================== ConvT 2x2 weight gradient, transposed LDS reads ==============================
+// The ConvTranspose2d(k = 2, s = 2) weight gradient (diffusion_utilities.py:86):
+// dW[ci][ij][co] = sum_{n,h,w} X[n,h,w][ci] dY[n,2h+i,2w+j][co]; K = the pixels of the input grid H x W, rows M = Cin,
+// columns N = 4 sub-pixels x Cout; the slab layout [z][ci][ij * Cout + co] of cdm_convT2x2_wgrad.
 // Both operands are stored pixel-major in HBM (channels contiguous), i.e. k-strided for the MFMA.  They
 // are staged exactly as they arrive — float4 along channels, split into bf16 terms, one [16 pix][128 ch]
 // image per term (256-byte rows, 16-byte chunks XOR-swizzled by row: conflict-free stores and reads) —
 // and the k-contiguous MFMA fragments are produced by the hardware transpose read ds_read_b64_tr_b16
-// (two per fragment).  Block: 128 co x 128 columns of one tap (Cin % 128 == 0, Cout % 128 == 0), 4 waves
-// 2x2 of 64x64, split-K over blockIdx.z.  The 16 pixels of a K step lie in one image row (W % 16 == 0),
-// so the tap shift is one bounds test per pixel.  KS K steps (16 pixels each) share one barrier interval.
+// (two per fragment), instead of the generic GEMM's 8 scalar k-strided loads per column (0.19 of the h3 ceiling,
+// round 4).  Block: 128 ci x 128 columns of one sub-pixel (Cin % 128 == 0, Cout % 128 == 0), 4 waves 2x2 of 64x64,
+// split-K.  The 16 pixels of a K step lie in one image row (W % 16 == 0); dY is read at the sub-pixel (i, j) =
+// (tap >> 1, tap & 1) of each input pixel.  (The 3x3 per-tap weight gradient this staging was written for gave way to
+// the kernel-row kernel below)
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 static __device__ __forceinline__ int trswz(int row, int ch) {   // byte offset of 16-B chunk ch in row
     return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
 }
 
-// CT (round 5): the ConvTranspose2d(k = 2, s = 2) weight gradient on the same staging (diffusion_utilities.py:86):
-// dW[ci][ij][co] = sum_{n,h,w} X[n,h,w][ci] dY[n,2h+i,2w+j][co] — "dy" is then the ConvT input X (rows M = its
-// channels), "x" its output gradient dY read at the sub-pixel (i, j) = (tap >> 1, tap & 1) of each input pixel (N =
-// 4 taps x its channels), H / W the input grid; the slab layout [z][ci][ij * Cout + co] of cdm_convT2x2_wgrad.  Both
-// operands are staged pixel-major as they arrive and read transposed, instead of the generic GEMM's 8 scalar
-// k-strided loads per column (0.19 of the h3 ceiling, round 4).
-template <int NT, int KS = 1, bool CT = false>   // KS = 2 measured neutral (1.06 vs 1.07 ms per 309 GF)
-__global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float* __restrict__ dy, int lddy, int Cout,
-                                                                     const float* __restrict__ x, int H, int W, int Cin,
-                                                                     int ldx, int K, int kt_per_split,
-                                                                     const float* amax_dy, const float* amax_x,
-                                                                     EpiStore ep) {
+template <int NT>   // NT_H3 or 1 (the x16 arithmetics)
+__global__ __launch_bounds__(GTHREADS, 2) void convT2x2_wgrad_tr_kernel(const float* __restrict__ x, int ldx, int Cin,
+                                                                        const float* __restrict__ dy, int H, int W,
+                                                                        int Cout, int lddy, int K, int kt_per_split,
+                                                                        const float* amax_x, const float* amax_dy,
+                                                                        EpiStore ep) {
+    static_assert(NT == NT_H3 || NT == 1, "x16 arithmetics only");
     constexpr int NS = XTerms<NT>::NS;
     constexpr int IMG = 16 * 128;                     // bf16 per [16 pix][128 ch] term image
     constexpr int STEP = 2 * NS * IMG;                // bf16 per K step (both operands, all terms)
-    __shared__ __attribute__((aligned(16))) __bf16 smem[2 * KS * STEP];
+    __shared__ __attribute__((aligned(16))) __bf16 smem[2 * STEP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     // 1-D grid, split-major logical order L = z*T + tile, remapped so that each XCD (hardware block b -> XCD b%8)
-    // runs a contiguous range of L: the T tiles of one split share their dY / X pixel range in that XCD's L2.
-    constexpr int NTAP = CT ? 4 : 9;
-    const int gx = Cout / GBM, T = gx * (NTAP * Cin / GBN);
+    // runs a contiguous range of L: the T tiles of one split share their X / dY pixel range in that XCD's L2.
+    const int gx = Cin / GBM, T = gx * (4 * Cout / GBN);
     int L;
     {
         const int nwg = gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -1734,13 +1733,12 @@ __global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float
     }
     const int bz = L / T, tl = L - bz * T;
     const int m0 = (tl % gx) * GBM, n0 = (tl / gx) * GBN;
-    const int tap = n0 / Cin, ci0 = n0 - tap * Cin;
-    const int ky = tap / 3, sdy = ky - 1, sdx = tap - ky * 3 - 1;
-    const int ti = tap >> 1, tj = tap & 1;            // CT: the sub-pixel of the output gradient
+    const int tap = n0 / Cout, co0 = n0 - tap * Cout;
+    const int ti = tap >> 1, tj = tap & 1;            // the sub-pixel of the output gradient
     const int ktiles = K / 16;
     const int kt0 = bz * kt_per_split;
     const int kt1 = min(ktiles, kt0 + kt_per_split);
-    const float sdy_ = op_scale<NT>(amax_dy), sx_ = op_scale<NT>(amax_x);
+    const float sx_ = op_scale<NT>(amax_x), sdy_ = op_scale<NT>(amax_dy);
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -1756,53 +1754,37 @@ __global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float
     // running image coordinates of the K step's first pixel
     int p0 = kt0 * 16;
     int pn = p0 / hw, ph = (p0 - pn * hw) / W, pw = p0 - pn * hw - ph * W;
-    // DEEP2 (CT, KS = 1; round 6): two register sets, the K step two ahead in flight while one computes — a ConvT K step
-    // is 12 MFMAs per wave, far too short to cover the HBM latency of loads issued one step ahead
-    constexpr bool DEEP2 = CT && KS == 1;
-    float4 ra[KS][2], rb[KS][2], ra2[DEEP2 ? KS : 1][2], rb2[DEEP2 ? KS : 1][2];
-    auto gload_to = [&](float4 (&ra)[KS][2], float4 (&rb)[KS][2], int kt) {   // the KS K steps from kt (zero past kt1)
+    // two register sets, the K step two ahead in flight while one computes (round 6) — a ConvT K step is 12 MFMAs per
+    // wave, far too short to cover the HBM latency of loads issued one step ahead
+    float4 ra[2], rb[2], ra2[2], rb2[2];
+    auto gload_to = [&](float4 (&ra)[2], float4 (&rb)[2], int kt) {   // the K step kt (zero past kt1)
+        const bool ok = kt < kt1;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const bool ok = kt + ks < kt1;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int kk = kq + 8 * i;
-                const long long pix = (long long)(pn * H + ph) * W + pw + kk;
-                ra[ks][i] = ok ? ld4(dy + pix * lddy + m0 + c4) : f4zero();
-                if constexpr (CT) {
-                    const long long opix = (long long)(pn * 2 * H + 2 * ph + ti) * (2 * W) + 2 * (pw + kk) + tj;
-                    rb[ks][i] = ok ? ld4(x + opix * ldx + ci0 + c4) : f4zero();
-                } else {
-                    const int hh = ph + sdy, ww = pw + kk + sdx;
-                    rb[ks][i] = (ok && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
-                                    ? ld4(x + ((long long)(pn * H + hh) * W + ww) * ldx + ci0 + c4)
-                                    : f4zero();
-                }
-            }
-            pw += 16;
-            if (pw >= W) { pw = 0; if (++ph == H) { ph = 0; ++pn; } }
+        for (int i = 0; i < 2; ++i) {
+            const int kk = kq + 8 * i;
+            const long long pix = (long long)(pn * H + ph) * W + pw + kk;
+            ra[i] = ok ? ld4(x + pix * ldx + m0 + c4) : f4zero();
+            const long long opix = (long long)(pn * 2 * H + 2 * ph + ti) * (2 * W) + 2 * (pw + kk) + tj;
+            rb[i] = ok ? ld4(dy + opix * lddy + co0 + c4) : f4zero();
         }
+        pw += 16;
+        if (pw >= W) { pw = 0; if (++ph == H) { ph = 0; ++pn; } }
     };
-    auto gload = [&](int kt) { gload_to(ra, rb, kt); };
-    auto sstore_from = [&](const float4 (&ra)[KS][2], const float4 (&rb)[KS][2], __bf16* base0) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
+    auto sstore_from = [&](const float4 (&ra)[2], const float4 (&rb)[2], __bf16* base) {
 #pragma unroll
         for (int op = 0; op < 2; ++op)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                __bf16* base = base0 + ks * STEP;
-                const float4 v = op ? rb[ks][i] : ra[ks][i];
+                const float4 v = op ? rb[i] : ra[i];
                 const float xv[4] = {v.x, v.y, v.z, v.w};
                 u32x2 tm[3];
-                split_pk4<NT>(xv, op ? sx_ : sdy_, tm);
+                split_pk4<NT>(xv, op ? sdy_ : sx_, tm);
                 const int kk = kq + 8 * i;
                 char* d = reinterpret_cast<char*>(base + op * NS * IMG) + trswz(kk, c4 >> 3) + (c4 & 7) * 2;
 #pragma unroll
                 for (int k = 0; k < NS; ++k) *reinterpret_cast<u32x2*>(d + k * IMG * 2) = tm[k];
             }
     };
-    auto sstore = [&](__bf16* base0) { sstore_from(ra, rb, base0); };
     // transposed-read addresses: lane 4q+p of 16-lane group g supplies row kb+q, columns c0+4p..+3
     const int g = (lane >> 4) & 3, q = (lane >> 2) & 3, pq = lane & 3;
     const int kb = 8 * (g >> 1) + q;
@@ -1818,9 +1800,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float
     }
 
     auto mma_at = [&](int cur) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-        const char* a = reinterpret_cast<const char*>(smem + (cur * KS + ks) * STEP);
+        const char* a = reinterpret_cast<const char*>(smem + cur * STEP);
         const char* b = a + NS * IMG * 2;
         bf16x8 fa[2][NS], fb[2][NS];
 #pragma unroll
@@ -1839,51 +1819,31 @@ __global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f32x16 c = acc[i][j];
-                if constexpr (NT >= 6) {
-                    c = xmfma<NT>(fa[i][1], fb[j][1], c);
-                    c = xmfma<NT>(fa[i][2], fb[j][0], c);
-                    c = xmfma<NT>(fa[i][0], fb[j][2], c);
-                }
                 if constexpr (NT >= 3) {
                     c = xmfma<NT>(fa[i][1], fb[j][0], c);
                     c = xmfma<NT>(fa[i][0], fb[j][1], c);
                 }
                 acc[i][j] = xmfma<NT>(fa[i][0], fb[j][0], c);
             }
-        }
     };
-    if constexpr (DEEP2) {
-        if (kt0 < kt1) { gload_to(ra, rb, kt0); sstore_from(ra, rb, smem); }
-        if (kt0 + 1 < kt1) gload_to(ra2, rb2, kt0 + 1);
+    if (kt0 < kt1) { gload_to(ra, rb, kt0); sstore_from(ra, rb, smem); }
+    if (kt0 + 1 < kt1) gload_to(ra2, rb2, kt0 + 1);
+    __syncthreads();
+    int cur = 0;
+    for (int kt = kt0; kt < kt1; kt += 2) {   // set (ra, rb): even steps, (ra2, rb2): odd steps
+        if (kt + 2 < kt1) gload_to(ra, rb, kt + 2);
+        mma_at(cur);
+        if (kt + 1 < kt1) sstore_from(ra2, rb2, smem + (cur ^ 1) * STEP);
         __syncthreads();
-        int cur = 0;
-        for (int kt = kt0; kt < kt1; kt += 2) {   // set (ra, rb): even steps, (ra2, rb2): odd steps
-            if (kt + 2 < kt1) gload_to(ra, rb, kt + 2);
-            mma_at(cur);
-            if (kt + 1 < kt1) sstore_from(ra2, rb2, smem + (cur ^ 1) * STEP);
-            __syncthreads();
-            cur ^= 1;
-            if (kt + 1 >= kt1) break;
-            if (kt + 3 < kt1) gload_to(ra2, rb2, kt + 3);
-            mma_at(cur);
-            if (kt + 2 < kt1) sstore_from(ra, rb, smem + (cur ^ 1) * STEP);
-            __syncthreads();
-            cur ^= 1;
-        }
-    } else {
-        if (kt0 < kt1) { gload(kt0); sstore(smem); }
+        cur ^= 1;
+        if (kt + 1 >= kt1) break;
+        if (kt + 3 < kt1) gload_to(ra2, rb2, kt + 3);
+        mma_at(cur);
+        if (kt + 2 < kt1) sstore_from(ra, rb, smem + (cur ^ 1) * STEP);
         __syncthreads();
-        int cur = 0;
-        for (int kt = kt0; kt < kt1; kt += KS) {
-            const bool more = kt + KS < kt1;
-            if (more) gload(kt + KS);
-            mma_at(cur);
-            if (more) sstore(smem + (cur ^ 1) * KS * STEP);
-            __syncthreads();
-            cur ^= 1;
-        }
+        cur ^= 1;
     }
-    unscale<NT>(acc, sdy_, sx_);
+    unscale<NT>(acc, sx_, sdy_);
     EpiStore e = ep;                       // this block's split slab (the epilogue would index blockIdx.z)
     e.y += (long long)bz * ep.zstride;
     e.zstride = 0;
@@ -1894,8 +1854,8 @@ __global__ __launch_bounds__(GTHREADS, 2) void wgrad3x3_tr_x3_kernel(const float
 // Per K step (16 pixels of one image row) it stages dY [16 pix][128 co] and the input row segment with its
 // 1-pixel halo X [18 pix][128 ci] once; the 3 taps read B from the same X image at row offsets 0 / 1 / 2 (the
 // kx shift), so each dY fragment feeds 3 taps and X is staged once instead of three times (2.5x less LDS
-// traffic per MFMA than the per-tap kernel above).  8 waves = 2 (co) x 4 (ci), wave tile 64 co x 32 ci x 3
-// taps (6 accumulators).  Split-K over pixel ranges; writes slab[z][co][tap*Cin+ci] like the per-tap kernel.
+// traffic per MFMA than the retired per-tap kernel).  8 waves = 2 (co) x 4 (ci), wave tile 64 co x 32 ci x 3
+// taps (6 accumulators).  Split-K over pixel ranges; writes slab[z][co][tap*Cin+ci].
 template <int NT, int KS = 1, class PRE = PreNone, class PX = PreNone, class GT = float, class XT = float>
                                 // GT / XT: element types of dy (g and PRE's y) / of x (and PX's g): bf16 for C4's
                                 // fused-chain activations and gradients
@@ -1928,7 +1888,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_row_kernel(const GT* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = UNI ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int gx = Cout / 128, T = gx * 3 * (Cin / 128);
-    int L;   // split-major logical order, XCD-contiguous ranges (as the per-tap kernel)
+    int L;   // split-major logical order, XCD-contiguous ranges (as convT2x2_wgrad_tr_kernel)
     {
         const int nwg = gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
         L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
@@ -2157,7 +2117,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_row_kernel(const GT* __restri
             if (tid < 64) put(b, RA + sr, xpre(x1, vb1), sb, IB);
         }
     };
-    // transposed-read addresses (see the per-tap kernel); tap t reads X rows shifted by t
+    // transposed-read addresses (see convT2x2_wgrad_tr_kernel); tap t reads X rows shifted by t
     const int g = (lane >> 4) & 3, q = (lane >> 2) & 3, pq = lane & 3;
     const int kb = 8 * (g >> 1) + q;
     // (the swizzle depends on row & 15 only: K sub-step k adds the constant 16 k rows = 4096 k bytes)

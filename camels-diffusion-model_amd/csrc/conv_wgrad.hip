@@ -1,4 +1,4 @@
-// conv3x3 weight gradient (kernel-row and transposed-read kernels, split-GEMM fallback): C ABI.  Kernels: conv_kernels.h.
+// conv3x3 weight gradient (kernel-row kernel, split-GEMM fallback): C ABI.  Kernels: conv_kernels.h.
 #include "conv_kernels.h"
 
 // the staggered wave order of the kernel-row weight gradient ($CDM_WGRAD_STAGGER, default 5 since round 6).  Round 3's
@@ -75,34 +75,16 @@ static int launch_wgrad_row(const GT* dy, int lddy, int Cout, const XT* x, int H
 // conv3x3 weight gradient on the 16-bit matrix cores (same slab contract as cdm_conv3x3_wgrad); W % 8 == 0
 static int conv3x3_wgrad_split(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin,
                                int ldx, const float* amax_dy, const float* amax_x, int splits, float* slab, int nterm,
-                               hipStream_t st, int variant = 0) {
+                               hipStream_t st) {
     if (Cin % 4 || Cout % 4 || W % 8) return (int)hipErrorInvalidValue;
     const int M = Cout, NN = 9 * Cin, K = N * H * W;
     const int sp = effective_splits(K, splits);
     EpiStore ep{slab, NN, (long long)M * NN, nullptr, 1, 0, nullptr, 0, M, NN};
-    const bool row_ok = Cin % 128 == 0 && Cout % 128 == 0 && lddy % 4 == 0 && ldx % 4 == 0;
-    if ((variant == 0 || variant == 3) && row_ok) {   // kernel-row path (3 taps per block): KS = 2, else 1
-        if (variant == 0 && W % 32 == 0 && effective_splits(K, splits, 32) == sp)
+    if (Cin % 128 == 0 && Cout % 128 == 0 && lddy % 4 == 0 && ldx % 4 == 0) {   // kernel-row path (3 taps per block)
+        if (W % 32 == 0 && effective_splits(K, splits, 32) == sp)               // 32-pixel K steps, else 16
             return launch_wgrad_row<2>(dy, lddy, Cout, x, H, W, Cin, ldx, K, sp, amax_dy, amax_x, slab, nterm, st);
         if (W % 16 == 0 && effective_splits(K, splits, 16) == sp)
             return launch_wgrad_row<1>(dy, lddy, Cout, x, H, W, Cin, ldx, K, sp, amax_dy, amax_x, slab, nterm, st);
-    }
-    if (variant != 2 && Cin % 128 == 0 && Cout % 128 == 0 && W % 16 == 0 && lddy % 4 == 0 && ldx % 4 == 0 &&
-        effective_splits(K, splits, 16) == sp) {   // transposed-read path
-        const int ktiles = K / 16, per = (ktiles + sp - 1) / sp;
-        dim3 grid((M / GBM) * (NN / GBN) * ((ktiles + per - 1) / per));
-        switch (nterm) {
-            case 1: hipLaunchKernelGGL(wgrad3x3_tr_x3_kernel<1>, grid, dim3(GTHREADS), 0, st, dy, lddy, Cout, x, H, W, Cin,
-                                       ldx, K, per, amax_dy, amax_x, ep); break;
-            case 3: hipLaunchKernelGGL(wgrad3x3_tr_x3_kernel<3>, grid, dim3(GTHREADS), 0, st, dy, lddy, Cout, x, H, W, Cin,
-                                       ldx, K, per, amax_dy, amax_x, ep); break;
-            case NT_H3: hipLaunchKernelGGL(wgrad3x3_tr_x3_kernel<NT_H3>, grid, dim3(GTHREADS), 0, st, dy, lddy, Cout, x, H,
-                                           W, Cin, ldx, K, per, amax_dy, amax_x, ep); break;
-            case 6: hipLaunchKernelGGL(wgrad3x3_tr_x3_kernel<6>, grid, dim3(GTHREADS), 0, st, dy, lddy, Cout, x, H, W, Cin,
-                                       ldx, K, per, amax_dy, amax_x, ep); break;
-            default: return (int)hipErrorInvalidValue;
-        }
-        return cdm_status();
     }
     return launch_gemm_x3<ColK<LdDenseAT>::template T, ColK<LdIm2colB>::template T, EpiStore, false>(
         MkColK<LdDenseAT>{LdDenseAT{dy, lddy, M, K}, amax_dy}, MkColK<LdIm2colB>{LdIm2colB{x, H, W, Cin, ldx, K, NN}, amax_x},
@@ -121,67 +103,11 @@ CDM_API int cdm_conv3x3_wgrad_x16(const float* dy, int lddy, int Cout, const flo
     if (!x16_ok(nterm) || !x16_amax_ok(nterm, amax_dy, amax_x)) return (int)hipErrorInvalidValue;
     return conv3x3_wgrad_split(dy, lddy, Cout, x, N, H, W, Cin, ldx, amax_dy, amax_x, splits, slab, nterm, S(stream));
 }
-CDM_API int cdm_conv3x3_wgrad_h3(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin,
-                                 int ldx, const float* amax_dy, const float* amax_x, int splits, float* slab,
-                                 void* stream) {
-    return cdm_conv3x3_wgrad_x16(dy, lddy, Cout, x, N, H, W, Cin, ldx, amax_dy, amax_x, splits, slab, NT_H3, stream);
-}
-
-// measurement entry: variant 0 = kernel-row kernel, 32-pixel K steps (default path), 1 = per-tap kernel,
-// 2 = generic split GEMM, 3 = kernel-row kernel with 16-pixel K steps
-CDM_API int cdm_conv3x3_wgrad_h3_variant(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W,
-                                         int Cin, int ldx, const float* amax_dy, const float* amax_x, int splits,
-                                         float* slab, int variant, void* stream) {
-    if (!amax_dy || !amax_x || variant < 0 || variant > 3) return (int)hipErrorInvalidValue;
-    return conv3x3_wgrad_split(dy, lddy, Cout, x, N, H, W, Cin, ldx, amax_dy, amax_x, splits, slab, NT_H3, S(stream),
-                               variant);
-}
-
-// conv3x3 weight gradient of a Conv -> BatchNorm -> ReLU layer with the BN backward fused into the dY staging of
-// the kernel-row kernel (same slab contract as cdm_conv3x3_wgrad_h3).  Cin % 128 == Cout % 128 == 0, W % 16 == 0.
-CDM_API int cdm_conv3x3_wgrad_x16_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s,
-                                        const float* t, const float* mean, const float* invstd, const float* A,
-                                        const float* B, const float* Cc, int Cout, const float* x, int N, int H, int W,
-                                        int Cin, int ldx, const float* amax_dy, const float* amax_x, int splits,
-                                        float* slab, int nterm, int dt, void* stream) {
-    if (!x16_ok(nterm) || Cin % 128 || Cout % 128 || W % 16 || ldg % 4 || ldy % 4 || ldx % 4 ||
-        !x16_amax_ok(nterm, amax_dy, amax_x) || (dt && nterm != 1))
-        return (int)hipErrorInvalidValue;
-    const int K = N * H * W, sp = effective_splits(K, splits);
-    const PreBnBwd pre{y, ldy, {s, t, mean, invstd, A, B, Cc}};
-    // dt bit 0: g and y are bf16, bit 1: x is bf16
-    auto run = [&](auto gtag, auto xtag) {
-        using GT = decltype(gtag);
-        using XT = decltype(xtag);
-        const GT* gg = reinterpret_cast<const GT*>(g);
-        const XT* xx = reinterpret_cast<const XT*>(x);
-        if (W % 32 == 0 && effective_splits(K, splits, 32) == sp)
-            return launch_wgrad_row<2>(gg, ldg, Cout, xx, H, W, Cin, ldx, K, sp, amax_dy, amax_x, slab, nterm, S(stream),
-                                       pre);
-        if (effective_splits(K, splits, 16) == sp)
-            return launch_wgrad_row<1>(gg, ldg, Cout, xx, H, W, Cin, ldx, K, sp, amax_dy, amax_x, slab, nterm, S(stream),
-                                       pre);
-        return (int)hipErrorInvalidValue;
-    };
-    switch (dt & 3) {
-        case 1: return run(__bf16{}, float{});
-        case 2: return run(float{}, __bf16{});
-        case 3: return run(__bf16{}, __bf16{});
-        default: return run(float{}, float{});
-    }
-}
-CDM_API int cdm_conv3x3_wgrad_h3_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s,
-                                       const float* t, const float* mean, const float* invstd, const float* A,
-                                       const float* B, const float* Cc, int Cout, const float* x, int N, int H, int W,
-                                       int Cin, int ldx, const float* amax_dy, const float* amax_x, int splits,
-                                       float* slab, void* stream) {
-    return cdm_conv3x3_wgrad_x16_bnbwd(g, ldg, y, ldy, s, t, mean, invstd, A, B, Cc, Cout, x, N, H, W, Cin, ldx, amax_dy,
-                                       amax_x, splits, slab, NT_H3, 0, stream);
-}
 
 // the kernel-row weight gradient with both staging fusions selectable: g / y / BN coefficients (optional, all or
-// none: the dY operand is the BN backward of g, as cdm_conv3x3_wgrad_h3_bnbwd) and x_s / x_t (optional: the X operand
-// is relu(x * x_s[c] + x_t[c]) of the previous layer's pre-norm output).  Cin % 128 == Cout % 128 == 0, W % 16 == 0.
+// none: the dY operand is the BN backward of g, bn_bwd_elem per staged element, dY never written) and x_s / x_t
+// (optional: the X operand is relu(x * x_s[c] + x_t[c]) of the previous layer's pre-norm output).  Cin % 128 ==
+// Cout % 128 == 0, W % 16 == 0.
 CDM_API int cdm_conv3x3_wgrad_x16_ex(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
                                      const float* mean, const float* invstd, const float* A, const float* B,
                                      const float* Cc, int Cout, const float* x, int N, int H, int W, int Cin, int ldx,
@@ -243,12 +169,4 @@ CDM_API int cdm_conv3x3_wgrad_x16_ex(const float* g, int ldg, const float* y, in
         case 3: return run(__bf16{}, __bf16{});
         default: return run(float{}, float{});
     }
-}
-CDM_API int cdm_conv3x3_wgrad_h3_ex(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                                    const float* mean, const float* invstd, const float* A, const float* B,
-                                    const float* Cc, int Cout, const float* x, int N, int H, int W, int Cin, int ldx,
-                                    const float* x_s, const float* x_t, const float* amax_dy, const float* amax_x,
-                                    int splits, float* slab, void* stream) {
-    return cdm_conv3x3_wgrad_x16_ex(g, ldg, y, ldy, s, t, mean, invstd, A, B, Cc, Cout, x, N, H, W, Cin, ldx, x_s, x_t,
-                                    nullptr, 0, nullptr, nullptr, nullptr, amax_dy, amax_x, splits, slab, NT_H3, 0, stream);
 }

@@ -193,53 +193,34 @@ __global__ __launch_bounds__(256) void slab_reduce4_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/cdm_hip.h)
 // ---------------------------------------------------------------------------------------------
-template <int BK, int KC, bool XCD>
-static int conv3x3_fwd_bk(const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk, const float* bias,
-                          float* y, int ldy, int Cout, int flags, float* stats, int stats_ld, hipStream_t st) {
+// fp32 conv3x3 forward as an implicit GEMM with the XCD-aware M-tile remap; KC = K order of the packed weights
+template <int KC>
+static int conv3x3_fwd_f32(const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk, const float* bias,
+                           float* y, int ldy, int Cout, int flags, float* stats, int stats_ld, hipStream_t st) {
     const int M = N * H * W, K = 9 * Cin;
     LdDenseB lb{wpk, Cout, K, Cout};
     EpiStore ep{y, ldy, 0, bias, Cout, flags, stats, stats_ld, M, Cout};
     if (Cin == 128 && Cout == 128 && H == 64 && W == 64) {   // the hot conv: own instantiation
         LdIm2colA<128, KC, 64> la{x, H, W, Cin, ldx, M, K};
-        return launch_gemm<LdIm2colA<128, KC, 64>, LdDenseB, EpiStore, false, BK, XCD>(la, lb, ep, M, Cout, K, 1, st);
+        return launch_gemm<LdIm2colA<128, KC, 64>, LdDenseB, EpiStore, false, true>(la, lb, ep, M, Cout, K, 1, st);
     }
     if (Cin == 128 && Cout == 128) {
         LdIm2colA<128, KC> la{x, H, W, Cin, ldx, M, K};
-        return launch_gemm<LdIm2colA<128, KC>, LdDenseB, EpiStore, false, BK, XCD>(la, lb, ep, M, Cout, K, 1, st);
+        return launch_gemm<LdIm2colA<128, KC>, LdDenseB, EpiStore, false, true>(la, lb, ep, M, Cout, K, 1, st);
     }
     LdIm2colA<0, KC> la{x, H, W, Cin, ldx, M, K};
-    return launch_gemm<LdIm2colA<0, KC>, LdDenseB, EpiStore, false, BK, XCD>(la, lb, ep, M, Cout, K, 1, st);
+    return launch_gemm<LdIm2colA<0, KC>, LdDenseB, EpiStore, false, true>(la, lb, ep, M, Cout, K, 1, st);
 }
 
 // kc = K order of the packed weights (cdm_pack_conv3x3): 16 = channel-chunk-major (needs Cin % 16 == 0),
-// 0 = tap-major.  Both run with the XCD-aware M-tile remap.
+// 0 = tap-major.
 CDM_API int cdm_conv3x3_fwd(const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk,
                             const float* bias, float* y, int ldy, int Cout, int flags, float* stats, int stats_ld,
                             int kc, void* stream) {
     if (Cin % 4 || Cout % 4 || (kc != 0 && kc != 16) || (kc == 16 && Cin % 16)) return (int)hipErrorInvalidValue;
     if (kc == 16)
-        return conv3x3_fwd_bk<16, 16, true>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld,
-                                            S(stream));
-    return conv3x3_fwd_bk<16, 0, true>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld,
-                                       S(stream));
-}
-
-// tuning entry point: 0 = default (BK16, tap-major K), 1 = BK32, 2 = XCD remap,
-// 3 = channel-chunk-major K (needs the kc=16 weight pack), 4 = 2 + 3
-CDM_API int cdm_conv3x3_fwd_variant(int variant, const float* x, int N, int H, int W, int Cin, int ldx,
-                                    const float* wpk, const float* bias, float* y, int ldy, int Cout, int flags,
-                                    float* stats, int stats_ld, void* stream) {
-    if (Cin % 4 || Cout % 4) return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    switch (variant) {
-        case 1: return conv3x3_fwd_bk<32, 0, false>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, st);
-        case 2: return conv3x3_fwd_bk<16, 0, true>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, st);
-        case 3: if (Cin % 16) return (int)hipErrorInvalidValue;
-                return conv3x3_fwd_bk<16, 16, false>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, st);
-        case 4: if (Cin % 16) return (int)hipErrorInvalidValue;
-                return conv3x3_fwd_bk<16, 16, true>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, st);
-        default: return conv3x3_fwd_bk<16, 0, false>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, st);
-    }
+        return conv3x3_fwd_f32<16>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, S(stream));
+    return conv3x3_fwd_f32<0>(x, N, H, W, Cin, ldx, wpk, bias, y, ldy, Cout, flags, stats, stats_ld, S(stream));
 }
 
 static int split_blocks(int K, int N) {
@@ -346,11 +327,6 @@ CDM_API int cdm_convT2x2_fwd_x16(const float* x, int N, int H, int W, int Cin, i
         MkRowK<LdDenseA>{LdDenseA{x, ldx, M, K}, amax_x}, MkPre{reinterpret_cast<const __bf16*>(wx), NN, amax_w}, ep,
         M, NN, K, 1, nterm, S(stream));
 }
-CDM_API int cdm_convT2x2_fwd_h3(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx,
-                                const float* amax_x, const float* amax_w, const float* bias, float* y, int ldy,
-                                int Cout, float* amax_y, void* stream) {
-    return cdm_convT2x2_fwd_x16(x, N, H, W, Cin, ldx, wx, amax_x, amax_w, bias, y, ldy, Cout, amax_y, NT_H3, stream);
-}
 
 // dX[n,h,w,ci] (+)= sum_{ij,co} dY[n,2h+i,2w+j,co] * W[ci][co][ij];  H, W are the INPUT (small) grid
 CDM_API int cdm_convT2x2_dgrad(const float* dy, int N, int H, int W, int Cout, int lddy, const float* wpkT,
@@ -403,11 +379,6 @@ CDM_API int cdm_convT2x2_dgrad_x16(const float* dy, int N, int H, int W, int Cou
         MkRowK<LdConvT2x2GatherA>{LdConvT2x2GatherA{dy, H, W, Cout, lddy, M, K}, amax_dy},
         MkPre{reinterpret_cast<const __bf16*>(wx), Cin, amax_w}, ep, M, Cin, K, 1, nterm, S(stream));
 }
-CDM_API int cdm_convT2x2_dgrad_h3(const float* dy, int N, int H, int W, int Cout, int lddy, const void* wx,
-                                  const float* amax_dy, const float* amax_w, float* dx, int lddx, int Cin, int flags,
-                                  void* stream) {
-    return cdm_convT2x2_dgrad_x16(dy, N, H, W, Cout, lddy, wx, amax_dy, amax_w, dx, lddx, Cin, flags, NT_H3, stream);
-}
 
 // h3 ConvT 2x2 weight gradient (same slab contract as cdm_convT2x2_wgrad); W % 8 == 0
 CDM_API int cdm_convT2x2_wgrad_x16(const float* x, int N, int H, int W, int Cin, int ldx, const float* dy, int Cout,
@@ -420,15 +391,14 @@ CDM_API int cdm_convT2x2_wgrad_x16(const float* x, int N, int H, int W, int Cin,
     EpiStore ep{slab, NN, (long long)M * NN, nullptr, 1, 0, nullptr, 0, M, NN};
     if (Cin % 128 == 0 && Cout % 128 == 0 && W % 16 == 0 && ldx % 4 == 0 && lddy % 4 == 0 &&
         effective_splits(K, splits, 16) == sp) {
-        // the transposed-read staging of the 3x3 weight gradient with the ConvT sub-pixel map (other shapes: the generic
-        // GEMM below)
+        // the transposed-read kernel (other shapes: the generic GEMM below)
         const int ktiles = K / 16, per = (ktiles + sp - 1) / sp;
         dim3 grid((M / GBM) * (NN / GBN) * ((ktiles + per - 1) / per));
         if (nterm == NT_H3)
-            hipLaunchKernelGGL((wgrad3x3_tr_x3_kernel<NT_H3, 1, true>), grid, dim3(GTHREADS), 0, S(stream), x, ldx, Cin,
+            hipLaunchKernelGGL(convT2x2_wgrad_tr_kernel<NT_H3>, grid, dim3(GTHREADS), 0, S(stream), x, ldx, Cin,
                                dy, H, W, Cout, lddy, K, per, amax_x, amax_dy, ep);
         else
-            hipLaunchKernelGGL((wgrad3x3_tr_x3_kernel<1, 1, true>), grid, dim3(GTHREADS), 0, S(stream), x, ldx, Cin, dy, H,
+            hipLaunchKernelGGL(convT2x2_wgrad_tr_kernel<1>, grid, dim3(GTHREADS), 0, S(stream), x, ldx, Cin, dy, H,
                                W, Cout, lddy, K, per, amax_x, amax_dy, ep);
         return cdm_status();
     }
@@ -436,11 +406,6 @@ CDM_API int cdm_convT2x2_wgrad_x16(const float* x, int N, int H, int W, int Cin,
         MkColK<LdDenseAT>{LdDenseAT{x, ldx, M, K}, amax_x},
         MkColK<LdConvT2x2GatherB>{LdConvT2x2GatherB{dy, H, W, Cout, lddy, K, NN}, amax_dy}, ep, M, NN, K, sp, nterm,
         S(stream));
-}
-CDM_API int cdm_convT2x2_wgrad_h3(const float* x, int N, int H, int W, int Cin, int ldx, const float* dy, int Cout,
-                                  int lddy, const float* amax_x, const float* amax_dy, int splits, float* slab,
-                                  void* stream) {
-    return cdm_convT2x2_wgrad_x16(x, N, H, W, Cin, ldx, dy, Cout, lddy, amax_x, amax_dy, splits, slab, NT_H3, stream);
 }
 
 // C[m][n] = A[m][k] . B[k][n] (+bias[n % bias_mod]).  splits > 1: writes raw partials to slab[z][M][N].

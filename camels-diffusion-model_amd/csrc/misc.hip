@@ -1917,4 +1917,4 @@ CDM_API int cdm_counter_add(int* ctr, int delta, void* stream) {
     return cdm_status();
 }
 CDM_API int cdm_device_sync() { return (int)hipDeviceSynchronize(); }
-CDM_API int cdm_abi_version() { return 1; }
+CDM_API int cdm_abi_version() { return 2; }

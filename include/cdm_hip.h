@@ -21,6 +21,10 @@ extern "C" {
 #define CDM_EPI_RELU 1
 #define CDM_EPI_ACCUM 2
 
+/* returns 2.  Version 1 -> 2: the convolution section lost its forwarding aliases (the `_h3` names that supplied
+ * nterm = 4, dt = 0; the `_bnbwd` names that supplied dy_out = NULL or that staged as cdm_conv3x3_wgrad_x16_ex does)
+ * and its two `_variant` measurement entries, with the kernels only those launched; DESIGN.md §3.3 lists each removed
+ * name with the call that replaces it.  cdm_conv3x3_fwd_h3 alone stays.  No surviving entry point changed. */
 int cdm_abi_version(void);
 int cdm_device_sync(void);
 
@@ -31,10 +35,6 @@ int cdm_device_sync(void);
  * kc must equal the kc the weights were packed with (cdm_pack_conv3x3). */
 int cdm_conv3x3_fwd(const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk, const float* bias,
                     float* y, int ldy, int Cout, int flags, float* stats, int stats_ld, int kc, void* stream);
-/* same, selecting a kernel variant (tuning: 0 default, 1 BK32, 2 XCD remap, 3 chunked K, 4 = 2+3) */
-int cdm_conv3x3_fwd_variant(int variant, const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk,
-                            const float* bias, float* y, int ldy, int Cout, int flags, float* stats, int stats_ld,
-                            void* stream);
 /* conv3x3 forward, fp32-accurate on the bf16 matrix cores: operands split into nterm-term bf16 sums
  * (nterm 6 = fp32-class, 3 = bf16x3, 1 = bf16); wx3 from cdm_split_bf16x3 of the packed weights.
  * Same semantics as cdm_conv3x3_fwd (nn.Conv2d(.,.,3,1,1) diffusion_utilities.py:27,34). */
@@ -46,22 +46,39 @@ int cdm_conv3x3_wgrad_x3(const float* dy, int lddy, int Cout, const float* x, in
                          int splits, float* slab, int nterm, void* stream);
 /* fp32 [K][N] (ld ldb) -> [ceil(K/16)][3][N][16] bf16 split terms hi/mid/lo */
 int cdm_split_bf16x3(const float* b, long long ldb, int K, int N, void* out, void* stream);
-/* fp32-class conv3x3 on the fp16 matrix cores ("h3"): each operand is scaled by a power of two derived
- * from its max |.| (device scalars amax_x / amax_w, see cdm_amax_f32) and split into fp16 hi + lo;
- * 3 cross products (hh, hl, lh) per MAC, fp32 accumulate, exact unscale.  wx from cdm_split_f16x2 of
- * the packed weights with the same amax_w.  Same semantics as cdm_conv3x3_fwd. */
+/* ---- 16-bit-arithmetic ("x16") convolutions --------------------------------------------------------------------
+ * `nterm` selects the arithmetic: NT_H3 = 4 ("h3", fp32-class on the fp16 matrix cores) or 1 (one bf16 term per operand,
+ * fp32 accumulate: BASELINE configuration C4, bf16 mixed precision, with every train-mode Conv -> BatchNorm -> ReLU
+ * fusion of the h3 path).
+ * h3: each operand is scaled by a power of two derived from its max |.| (device scalars amax_*, see cdm_amax_f32) and
+ * split into fp16 hi + lo; 3 cross products (hh, hl, lh) per MAC, fp32 accumulate, exact unscale.  Weight images come
+ * from cdm_split_f16x2 of the packed weights with the same amax_w.
+ * nterm = 1: the weight images come from cdm_split_bf16x3 (plane 0 is read) and the amax_* operand maxima are ignored
+ * (may be null).
+ * dt: bf16 activation storage of C4's fused Conv -> BatchNorm -> ReLU chain, one-term (nterm = 1) arithmetic only.
+ * Forward / dgrad: bit 0 = the source (x or g, and the BN staging's y) holds bf16, bit 1 = the output is stored as bf16
+ * (statistics / maxima of the stored values).  Weight gradient: bit 0 = g / dy (and y) are bf16, bit 1 = x (and x_g) are
+ * bf16.  dt = 0: fp32 everywhere (every other arithmetic).
+ * Reference ops: nn.Conv2d(.,.,3,1,1) diffusion_utilities.py:27,34 and its autograd; nn.ConvTranspose2d(Cin, Cout, 2, 2)
+ * diffusion_utilities.py:86. */
+/* conv3x3 forward, same semantics as cdm_conv3x3_fwd; amax_y (optional): running max|y| (atomic) */
+int cdm_conv3x3_fwd_x16(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx, const float* amax_x,
+                        const float* amax_w, const float* bias, float* y, int ldy, int Cout, int flags, float* stats,
+                        int stats_ld, int kc, float* amax_y, int nterm, int dt, void* stream);
+/* the plain h3 forward, = cdm_conv3x3_fwd_x16(..., 4, 0): the one retained alias, kept because the benchmark's conv
+ * probe calls it */
 int cdm_conv3x3_fwd_h3(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx, const float* amax_x,
                        const float* amax_w, const float* bias, float* y, int ldy, int Cout, int flags, float* stats,
                        int stats_ld, int kc, float* amax_y, void* stream);
-/* cdm_conv3x3_fwd_h3 with the train-mode Conv -> BatchNorm -> ReLU fusions (LDS-halo shapes only):
+/* cdm_conv3x3_fwd_x16 with the train-mode Conv -> BatchNorm -> ReLU fusions (LDS-halo shapes only):
  * pre_s / pre_t (optional): the input is relu(x * pre_s[c] + pre_t[c]) computed while staging (x = the previous
  * layer's pre-norm output; its BatchNorm apply is never materialised; *amax_x must be max of that input);
  * ymm (optional, needs stats): per output channel max / min of y as ordered-int keys ymm[c] / ymm[ymm_ld + c],
  * cleared by the caller to INT_MIN / INT_MAX (cdm_fill_i32); cdm_bn_fwd_finalize turns them into max|z| */
-int cdm_conv3x3_fwd_h3_ex(const float* x, int N, int H, int W, int Cin, int ldx, const float* pre_s, const float* pre_t,
-                          const void* wx, const float* amax_x, const float* amax_w, const float* bias, float* y, int ldy,
-                          int Cout, int flags, float* stats, int stats_ld, int kc, float* amax_y, int* ymm, int ymm_ld,
-                          void* stream);
+int cdm_conv3x3_fwd_x16_ex(const float* x, int N, int H, int W, int Cin, int ldx, const float* pre_s, const float* pre_t,
+                           const void* wx, const float* amax_x, const float* amax_w, const float* bias, float* y,
+                           int ldy, int Cout, int flags, float* stats, int stats_ld, int kc, float* amax_y, int* ymm,
+                           int ymm_ld, int nterm, int dt, void* stream);
 /* eval-mode conv3x3 of a Conv -> BatchNorm (folded into wx / bias) -> ReLU layer with its output transform in the
  * LDS-halo epilogue (csrc/conv_fwd_eval.hip; W == H in {32, 64}, kc = 16, Cout % 128 == 0), v = relu(conv + bias):
  *   kind 1 (resid, diffusion_utilities.py:54-55): y[p][c] = sc_w[s][c] sc_x[p] + sc_b[s][c] + v, s = image >= split
@@ -77,74 +94,32 @@ int cdm_conv3x3_fwd_x16_fused(const float* x, int N, int H, int W, int Cin, int 
  * block (0 -> 1) in place of the launcher's own policy */
 int cdm_conv3x3_halo_ablate(int abl, const float* x, int N, int H, int Cin, int ldx, const void* wx,
                             const float* amax_x, const float* amax_w, float* y, int ldy, int Cout, void* stream);
-int cdm_conv3x3_wgrad_h3(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin, int ldx,
-                         const float* amax_dy, const float* amax_x, int splits, float* slab, void* stream);
-/* measurement entry of the h3 weight gradient: variant 0 = kernel-row kernel (3 taps per block, 32-pixel K steps,
- * the default), 1 = per-tap kernel, 2 = generic split GEMM, 3 = kernel-row kernel with 16-pixel K steps; same
- * slab contract */
-int cdm_conv3x3_wgrad_h3_variant(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin,
-                                 int ldx, const float* amax_dy, const float* amax_x, int splits, float* slab,
-                                 int variant, void* stream);
-/* Conv -> BatchNorm -> ReLU backward with the BN backward fused into the conv staging (dy never written):
- * dy = A (y s + t > 0 ? g : 0) + B + Cc (y - mean) invstd per element (the expression of cdm_norm_apply_bwd
- * mode 0, bit-identical), s/t/mean/invstd/A/B/Cc per channel.  dgrad: LDS-halo kernel, W == H in {32, 64, 128},
- * C % 16 == 0, C <= 256, C = BN channels, Cout = dgrad output channels, wx = split packed dgrad weights;
- * wgrad: kernel-row kernel (Cin, Cout % 128 == 0, W % 16 == 0), same slab contract as cdm_conv3x3_wgrad_h3.
- * max|dy| <= *amax_dy from cdm_bn_bwd_amax_bound. */
-int cdm_conv3x3_dgrad_h3_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                               const float* mean, const float* invstd, const float* A, const float* B, const float* Cc,
-                               int N, int H, int W, int C, const void* wx, const float* amax_dy, const float* amax_w,
-                               float* out, int ldo, int Cout, int flags, float* amax_out, void* stream);
-int cdm_conv3x3_wgrad_h3_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                               const float* mean, const float* invstd, const float* A, const float* B, const float* Cc,
-                               int Cout, const float* x, int N, int H, int W, int Cin, int ldx, const float* amax_dy,
-                               const float* amax_x, int splits, float* slab, void* stream);
-/* the kernel-row weight gradient with both staging fusions selectable: y (+ s, t, mean, invstd, A, B, Cc) non-null:
- * dY = the BatchNorm backward of g (as cdm_conv3x3_wgrad_h3_bnbwd), else dY = g; x_s / x_t non-null: the X operand
- * is relu(x * x_s[c] + x_t[c]).  Cin % 128 == Cout % 128 == 0, W % 16 == 0. */
-int cdm_conv3x3_wgrad_h3_ex(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                            const float* mean, const float* invstd, const float* A, const float* B, const float* Cc,
-                            int Cout, const float* x, int N, int H, int W, int Cin, int ldx, const float* x_s,
-                            const float* x_t, const float* amax_dy, const float* amax_x, int splits, float* slab,
-                            void* stream);
-/* ---- the 16-bit-arithmetic ("x16") forms of the h3 entry points above and of the h3 ConvT 2x2 calls below ----------
- * identical contracts plus a trailing `nterm`: NT_H3 = 4 (fp32-class scaled fp16 hi/lo, = the *_h3 call) or 1 (one
- * bf16 term per operand, fp32 accumulate: BASELINE configuration C4, bf16 mixed precision, with every train-mode
- * Conv -> BatchNorm -> ReLU fusion of the h3 path).  For nterm = 1 the weight images come from cdm_split_bf16x3 (plane
- * 0 is read) and the amax_* operand maxima are ignored (may be null).  Reference ops: nn.Conv2d(.,.,3,1,1)
- * diffusion_utilities.py:27,34 and its autograd; nn.ConvTranspose2d(Cin, Cout, 2, 2) diffusion_utilities.py:86. */
-/* dt (the x16 conv entry points): bf16 activation storage of C4's fused Conv -> BatchNorm -> ReLU chain, one-term
- * (nterm = 1) arithmetic only.  Forward / dgrad: bit 0 = the source (x or g, and the BN staging's y) holds bf16, bit 1 =
- * the output is stored as bf16 (statistics / maxima of the stored values).  Weight gradient: bit 0 = g / dy (and y) are
- * bf16, bit 1 = x (and x_g) are bf16.  dt = 0: fp32 everywhere (every other arithmetic). */
-int cdm_conv3x3_fwd_x16(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx, const float* amax_x,
-                        const float* amax_w, const float* bias, float* y, int ldy, int Cout, int flags, float* stats,
-                        int stats_ld, int kc, float* amax_y, int nterm, int dt, void* stream);
-int cdm_conv3x3_fwd_x16_ex(const float* x, int N, int H, int W, int Cin, int ldx, const float* pre_s, const float* pre_t,
-                           const void* wx, const float* amax_x, const float* amax_w, const float* bias, float* y,
-                           int ldy, int Cout, int flags, float* stats, int stats_ld, int kc, float* amax_y, int* ymm,
-                           int ymm_ld, int nterm, int dt, void* stream);
+/* conv3x3 weight gradient, same slab contract as cdm_conv3x3_wgrad; W % 8 == 0.  Cin % 128 == Cout % 128 == 0 and
+ * W % 16 == 0: the kernel-row kernel (3 taps per block; 32-pixel K steps when W % 32 == 0, else 16), other shapes the
+ * generic split GEMM */
 int cdm_conv3x3_wgrad_x16(const float* dy, int lddy, int Cout, const float* x, int N, int H, int W, int Cin, int ldx,
                           const float* amax_dy, const float* amax_x, int splits, float* slab, int nterm, void* stream);
-int cdm_conv3x3_dgrad_x16_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                                const float* mean, const float* invstd, const float* A, const float* B, const float* Cc,
-                                int N, int H, int W, int C, const void* wx, const float* amax_dy, const float* amax_w,
-                                float* out, int ldo, int Cout, int flags, float* amax_out, int nterm, int dt,
-                                void* stream);
-/* the same, also storing the dy it computes into dy_out ([pix][C], g's row stride ldg and element type) for the
- * layer's weight gradient (cdm_conv3x3_wgrad_x16_ex with g = dy_out, y = null): the BN backward is evaluated once per
- * element instead of again in each of the weight gradient's 3 kernel-row blocks. */
+/* Conv -> BatchNorm -> ReLU backward, the data gradient, with the BN backward fused into the conv staging:
+ * dy = A (y s + t > 0 ? g : 0) + B + Cc (y - mean) invstd per element (the expression of cdm_norm_apply_bwd mode 0,
+ * bit-identical), s/t/mean/invstd/A/B/Cc per channel.  LDS-halo kernel, W == H in {32, 64, 128}, C % 16 == 0, C <= 256,
+ * C = BN channels, Cout = dgrad output channels, wx = split packed dgrad weights; max|dy| <= *amax_dy from
+ * cdm_bn_bwd_amax_bound.
+ * dy_out (optional): the dy computed in the staging is also stored there ([pix][C], g's row stride ldg and element
+ * type) for the layer's weight gradient (cdm_conv3x3_wgrad_x16_ex with g = dy_out, y = null): the BN backward is
+ * evaluated once per element instead of again in each of the weight gradient's 3 kernel-row blocks.  dy_out null: dy is
+ * never written. */
 int cdm_conv3x3_dgrad_x16_bnbwd_dy(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
                                    const float* mean, const float* invstd, const float* A, const float* B,
                                    const float* Cc, int N, int H, int W, int C, const void* wx, const float* amax_dy,
                                    const float* amax_w, float* out, int ldo, int Cout, int flags, float* amax_out,
                                    void* dy_out, int nterm, int dt, void* stream);
-int cdm_conv3x3_wgrad_x16_bnbwd(const float* g, int ldg, const float* y, int ldy, const float* s, const float* t,
-                                const float* mean, const float* invstd, const float* A, const float* B, const float* Cc,
-                                int Cout, const float* x, int N, int H, int W, int Cin, int ldx, const float* amax_dy,
-                                const float* amax_x, int splits, float* slab, int nterm, int dt, void* stream);
-/* cdm_conv3x3_wgrad_x16_ex also takes (x_g, ldxg, x_mean, x_invstd, x_sums), all optional (x_sums null: off): with
- * x_s / x_t given, the BatchNorm-backward channel sums of the layer that produced x are accumulated while x is staged:
+/* the kernel-row weight gradient with its staging fusions selectable (Cin % 128 == Cout % 128 == 0, W % 16 == 0; same
+ * slab contract as cdm_conv3x3_wgrad; K steps of 64, 32 or 16 pixels by W and the arithmetic):
+ * y (+ s, t, mean, invstd, A, B, Cc) non-null: dY = the BatchNorm backward of g, the expression of
+ * cdm_conv3x3_dgrad_x16_bnbwd_dy with max|dY| <= *amax_dy from cdm_bn_bwd_amax_bound (dY never written), else dY = g;
+ * x_s / x_t non-null: the X operand is relu(x * x_s[c] + x_t[c]) of the previous layer's pre-norm output x.
+ * (x_g, ldxg, x_mean, x_invstd, x_sums), all optional (x_sums null: off): with x_s / x_t given, the BatchNorm-backward
+ * channel sums of the layer that produced x are accumulated while x is staged:
  * g_pre = (x x_s + x_t > 0 ? x_g : 0), xhat = (x - x_mean) x_invstd; x_sums[(split * 3 + kernel row) * (Cout / 128) +
  * co tile][5][Cin] (one partial per block, splits = effective split count) rows 0 = sum g_pre, 1 = sum g_pre xhat,
  * 4 = sum xhat (rows 2, 3 zero) — the slab of cdm_norm_bwd_reduce mode 0 with 3 Cout/128 tiles per split
@@ -155,6 +130,10 @@ int cdm_conv3x3_wgrad_x16_ex(const float* g, int ldg, const float* y, int ldy, c
                              const float* x_t, const float* x_g, int ldxg, const float* x_mean, const float* x_invstd,
                              float* x_sums, const float* amax_dy, const float* amax_x, int splits, float* slab,
                              int nterm, int dt, void* stream);
+/* nn.ConvTranspose2d(Cin, Cout, 2, 2) forward and backward (same semantics as cdm_convT2x2_fwd / _dgrad / _wgrad
+ * below; H, W = input grid).  fwd: wx = the split image of wpk [Cin][4*Cout] with max|wpk| = *amax_w; dgrad: wx = the
+ * split image of wpkT [4 Cout][Cin] (max|W| = *amax_w), max|dy| = *amax_dy; wgrad: max|x| = *amax_x, max|dy| =
+ * *amax_dy, W % 8 == 0. */
 int cdm_convT2x2_fwd_x16(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx, const float* amax_x,
                          const float* amax_w, const float* bias, float* y, int ldy, int Cout, float* amax_y, int nterm,
                          void* stream);
@@ -207,10 +186,6 @@ int cdm_zero_f32(float* p, long long n, void* stream);
 /* nn.ConvTranspose2d(Cin,Cout,2,2) forward (diffusion_utilities.py:86); H,W = input grid. */
 int cdm_convT2x2_fwd(const float* x, int N, int H, int W, int Cin, int ldx, const float* wpk, const float* bias,
                      float* y, int ldy, int Cout, float* amax, void* stream);
-/* the same on the fp16 matrix cores (h3); wx = cdm_split_f16x2 of wpk [Cin][4*Cout] with max|wpk| = *amax_w */
-int cdm_convT2x2_fwd_h3(const float* x, int N, int H, int W, int Cin, int ldx, const void* wx, const float* amax_x,
-                        const float* amax_w, const float* bias, float* y, int ldy, int Cout, float* amax_y,
-                        void* stream);
 /* its input gradient (autograd of diffusion_utilities.py:86). */
 int cdm_convT2x2_dgrad(const float* dy, int N, int H, int W, int Cout, int lddy, const float* wpkT, float* dx,
                        int lddx, int Cin, int flags, void* stream);
@@ -230,13 +205,6 @@ int cdm_conv3x3_wgrad(const float* dy, int lddy, int Cout, const float* x, int N
                       int splits, float* slab, void* stream);
 int cdm_convT2x2_wgrad(const float* x, int N, int H, int W, int Cin, int ldx, const float* dy, int Cout, int lddy,
                        int splits, float* slab, void* stream);
-/* h3 variants of the ConvT 2x2 backward: dgrad with wx = cdm_split_f16x2 of wpkT [4 Cout][Cin] (max|W| = *amax_w)
- * and max|dy| = *amax_dy; wgrad with max|x| = *amax_x, max|dy| = *amax_dy (W % 8 == 0).  Same semantics. */
-int cdm_convT2x2_dgrad_h3(const float* dy, int N, int H, int W, int Cout, int lddy, const void* wx,
-                          const float* amax_dy, const float* amax_w, float* dx, int lddx, int Cin, int flags,
-                          void* stream);
-int cdm_convT2x2_wgrad_h3(const float* x, int N, int H, int W, int Cin, int ldx, const float* dy, int Cout, int lddy,
-                          const float* amax_x, const float* amax_dy, int splits, float* slab, void* stream);
 int cdm_gemm_tn_f32(const float* a, long long lda, int M, int K, const float* b, long long ldb, int N, int splits,
                     float* slab, void* stream);
 /* out[m*s_m + (n/csplit)*s_hi + (n%csplit)*s_lo] (+)= scale * sum_z slab[z][m][n] */
@@ -266,7 +234,7 @@ int cdm_bn_fwd_finalize(const double* part, int nparts, int R, int C, double cou
                         const float* beta, float* rmean, float* rvar, long long* nbt, double momentum, float eps,
                         float* mean, float* invstd, float* scale, float* shift, const int* ymm, int ymm_ld,
                         float* amax_z, void* stream);
-/* (ymm optional: the per-channel max / min keys of the layer's y from cdm_conv3x3_fwd_h3_ex; amax_z then receives
+/* (ymm optional: the per-channel max / min keys of the layer's y from cdm_conv3x3_fwd_x16_ex; amax_z then receives
  *  the exact max over the layer of relu(fmaf(y, scale, shift)) by an atomic max, for the consumer's h3 scale) */
 /* p[0..n) = v */
 int cdm_fill_i32(int* p, long long n, int v, void* stream);

@@ -148,7 +148,7 @@ def bn_relu_stage(x, s, t, to_bf16=False, f32ops=False):
 
 
 def bn_bwd_stage(g, y, s, t, mean, invstd, A, B, Cc, to_bf16=False, f32ops=False):
-    """dy = A (y s + t > 0 ? g : 0) + B + Cc (y - mean) invstd (include/cdm_hip.h, cdm_conv3x3_dgrad_h3_bnbwd);
+    """dy = A (y s + t > 0 ? g : 0) + B + Cc (y - mean) invstd (include/cdm_hip.h, cdm_conv3x3_dgrad_x16_bnbwd_dy);
     f32ops: the kernel's fp32 sequence zp = fmaf(y, s, t), xh = (y - mean) * invstd, fmaf(Cc, xh, fmaf(A, g', B))."""
     if f32ops:
         zp = fma32(y, s, t)

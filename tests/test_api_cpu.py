@@ -57,6 +57,8 @@ def test_library_exports_every_header_symbol():
     exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
     missing = set(protos) - exported
     assert not missing, missing
+    orphans = {n for n in exported if n.startswith("cdm_")} - set(protos)     # defined, but declared nowhere
+    assert not orphans, orphans
     assert len(protos) >= 45
 
 

@@ -134,8 +134,8 @@ def test_convT2x2(L, N, Hin, Cin, Cout):
     amx = _amax(L, xn, N * Hin * Hin, Cin)
     y3 = torch.empty_like(y)
     am3 = torch.zeros(1, device="cuda")
-    L.cdm_convT2x2_fwd_h3(xn.data_ptr(), N, Hin, Hin, Cin, Cin, wx.data_ptr(), amx.data_ptr(), amw.data_ptr(),
-                          bc.data_ptr(), y3.data_ptr(), Cout, Cout, am3.data_ptr(), _s())
+    L.cdm_convT2x2_fwd_x16(xn.data_ptr(), N, Hin, Hin, Cin, Cin, wx.data_ptr(), amx.data_ptr(), amw.data_ptr(),
+                           bc.data_ptr(), y3.data_ptr(), Cout, Cout, am3.data_ptr(), 4, _s())
     torch.cuda.synchronize()
     _close(_nchw(y3, N, 2 * Hin, 2 * Hin, Cout), ref.detach())
     assert am3.item() == y3.abs().max().item()
@@ -178,8 +178,8 @@ def test_convT2x2(L, N, Hin, Cin, Cout):
     amg = _amax(L, gyn, N * 4 * Hin * Hin, Cout)
     wxT, amwT = _split_h3(L, wtT, 4 * Cout, Cin)
     dx3 = torch.empty_like(dx)
-    L.cdm_convT2x2_dgrad_h3(gyn.data_ptr(), N, Hin, Hin, Cout, Cout, wxT.data_ptr(), amg.data_ptr(), amwT.data_ptr(),
-                            dx3.data_ptr(), Cin, Cin, 0, _s())
+    L.cdm_convT2x2_dgrad_x16(gyn.data_ptr(), N, Hin, Hin, Cout, Cout, wxT.data_ptr(), amg.data_ptr(), amwT.data_ptr(),
+                             dx3.data_ptr(), Cin, Cin, 0, 4, _s())
     torch.cuda.synchronize()
     _close(_nchw(dx3, N, Hin, Hin, Cin), xg.grad)
     # the input gradient on the two-deep prefetch GEMM vs gemm_x3, bit for bit (plain and accumulating epilogue)
@@ -190,8 +190,8 @@ def test_convT2x2(L, N, Hin, Cin, Cout):
         try:
             for flags in (0, 2):
                 o = base.clone()
-                L.cdm_convT2x2_dgrad_h3(gyn.data_ptr(), N, Hin, Hin, Cout, Cout, wxT.data_ptr(), amg.data_ptr(),
-                                        amwT.data_ptr(), o.data_ptr(), Cin, Cin, flags, _s())
+                L.cdm_convT2x2_dgrad_x16(gyn.data_ptr(), N, Hin, Hin, Cout, Cout, wxT.data_ptr(), amg.data_ptr(),
+                                         amwT.data_ptr(), o.data_ptr(), Cin, Cin, flags, 4, _s())
                 torch.cuda.synchronize()
                 got[deep, flags] = o
         finally:
@@ -201,8 +201,8 @@ def test_convT2x2(L, N, Hin, Cin, Cout):
     assert torch.equal(got["1", 0], dx3)
     if Hin % 8 == 0:
         slab.fill_(float("nan"))
-        L.cdm_convT2x2_wgrad_h3(xn.data_ptr(), N, Hin, Hin, Cin, Cin, gyn.data_ptr(), Cout, Cout, amx.data_ptr(),
-                                amg.data_ptr(), sp, slab.data_ptr(), _s())
+        L.cdm_convT2x2_wgrad_x16(xn.data_ptr(), N, Hin, Hin, Cin, Cin, gyn.data_ptr(), Cout, Cout, amx.data_ptr(),
+                                 amg.data_ptr(), sp, slab.data_ptr(), 4, _s())
         dW3 = torch.empty_like(dW)
         L.cdm_slab_reduce(slab.data_ptr(), sp, Cin, 4 * Cout, dW3.data_ptr(), 4 * Cout, 1, 4, Cout, 0, 1.0, _s())
         torch.cuda.synchronize()
@@ -330,8 +330,8 @@ def _conv_h3(L, x, W, b, gy, kc):
     assert amy.item() == y.abs().max().item()          # fused max|y| of the epilogue
     sp = L.raw("cdm_gemm_splits")(N * H * H, 5)
     slab = torch.empty(sp, Cout, 9 * Cin, device="cuda")
-    L.cdm_conv3x3_wgrad_h3(gyn.data_ptr(), Cout, Cout, xn.data_ptr(), N, H, H, Cin, Cin, amg.data_ptr(),
-                           amx.data_ptr(), sp, slab.data_ptr(), _s())
+    L.cdm_conv3x3_wgrad_x16(gyn.data_ptr(), Cout, Cout, xn.data_ptr(), N, H, H, Cin, Cin, amg.data_ptr(),
+                            amx.data_ptr(), sp, slab.data_ptr(), 4, _s())
     dW = torch.empty(Cout, Cin, 3, 3, device="cuda")
     L.cdm_slab_reduce(slab.data_ptr(), sp, Cout, 9 * Cin, dW.data_ptr(), 9 * Cin, 1, 9, Cin, 0, 1.0, _s())
     torch.cuda.synchronize()
@@ -405,8 +405,9 @@ def test_split_f16x2_terms(L):
                                        (1, 128, 256, 128), (256, 64, 128, 128), (256, 32, 256, 256)])
 def test_bn_bwd_fused_into_conv_staging_bit_exact(L, N, S, C, Cin):
     """Fused BN backward (dy computed while staging, never written) == norm_apply_bwd mode 0 then the h3
-    convs, bit for bit: dgrad (LDS-halo kernel) and wgrad (kernel-row kernel) at the same operand scale; the
-    scale comes from cdm_bn_bwd_amax_bound, which must bound max|dy|."""
+    convs, bit for bit: dgrad (LDS-halo kernel) and wgrad (kernel-row kernel, fused and plain dY staging of
+    cdm_conv3x3_wgrad_x16_ex) at the same operand scale; the scale comes from cdm_bn_bwd_amax_bound, which must bound
+    max|dy|.  The reduced weight gradients also agree with cdm_conv3x3_wgrad_x16 at the h3 tolerance."""
     from cdm_amd.engine import wgrad_splits
     g_ = torch.Generator(device="cuda").manual_seed(5)
     P = N * S * S
@@ -439,8 +440,8 @@ def test_bn_bwd_fused_into_conv_staging_bit_exact(L, N, S, C, Cin):
     a1 = torch.zeros(2, device="cuda")
     L.cdm_conv3x3_fwd_h3(dy.data_ptr(), N, S, S, C, C, wx.data_ptr(), dslot, amw.data_ptr(), None, ref.data_ptr(), Cin,
                          Cin, 0, None, 0, 16, a1.data_ptr(), _s())
-    L.cdm_conv3x3_dgrad_h3_bnbwd(gr.data_ptr(), C, y.data_ptr(), C, *coefs, N, S, S, C, wx.data_ptr(), dslot,
-                                 amw.data_ptr(), got.data_ptr(), Cin, Cin, 0, a1.data_ptr() + 4, _s())
+    L.cdm_conv3x3_dgrad_x16_bnbwd_dy(gr.data_ptr(), C, y.data_ptr(), C, *coefs, N, S, S, C, wx.data_ptr(), dslot,
+                                     amw.data_ptr(), got.data_ptr(), Cin, Cin, 0, a1.data_ptr() + 4, None, 4, 0, _s())
     torch.cuda.synchronize()
     assert torch.equal(got, ref)
     assert a1[0].item() == a1[1].item() == ref.abs().max().item()
@@ -455,12 +456,26 @@ def test_bn_bwd_fused_into_conv_staging_bit_exact(L, N, S, C, Cin):
     amx = _amax(L, x, P, Cin)
     sp = wgrad_splits(P, C, 9 * Cin)
     s_ref = torch.empty(sp, C, 9 * Cin, device="cuda"); s_got = torch.full_like(s_ref, float("nan"))
-    L.cdm_conv3x3_wgrad_h3(dy.data_ptr(), C, C, x.data_ptr(), N, S, S, Cin, Cin, dslot, amx.data_ptr(), sp,
-                           s_ref.data_ptr(), _s())
-    L.cdm_conv3x3_wgrad_h3_bnbwd(gr.data_ptr(), C, y.data_ptr(), C, *coefs, C, x.data_ptr(), N, S, S, Cin, Cin, dslot,
-                                 amx.data_ptr(), sp, s_got.data_ptr(), _s())
+    # both sides through cdm_conv3x3_wgrad_x16_ex with the same splits, so both take the same K step: the reference
+    # stages the stored dy plainly (null coefficients), the fused side stages g, y and the seven coefficients — the pair
+    # of forms the engine relies on (a fused layer's dgrad stores dy and the weight gradient stages it plainly)
+    nul = [None] * 7
+    tail = (C, x.data_ptr(), N, S, S, Cin, Cin, None, None, None, 0, None, None, None, dslot, amx.data_ptr(), sp)
+    L.cdm_conv3x3_wgrad_x16_ex(dy.data_ptr(), C, None, 0, *nul, *tail, s_ref.data_ptr(), 4, 0, _s())
+    L.cdm_conv3x3_wgrad_x16_ex(gr.data_ptr(), C, y.data_ptr(), C, *coefs, *tail, s_got.data_ptr(), 4, 0, _s())
     torch.cuda.synchronize()
     assert torch.equal(s_got, s_ref)
+    # and both, reduced, against the plain weight gradient of the same operands at the h3 tolerance (its dispatch may
+    # take another K step than the fused entry's at W = 64 and W = 128: close, not bit-equal)
+    s_pl = torch.empty_like(s_ref)
+    L.cdm_conv3x3_wgrad_x16(dy.data_ptr(), C, C, x.data_ptr(), N, S, S, Cin, Cin, dslot, amx.data_ptr(), sp,
+                            s_pl.data_ptr(), 4, _s())
+    dWs = [torch.empty(C, 9 * Cin, device="cuda") for _ in range(3)]
+    for slab, dW in zip((s_pl, s_ref, s_got), dWs):
+        L.cdm_slab_reduce(slab.data_ptr(), sp, C, 9 * Cin, dW.data_ptr(), 9 * Cin, 0, 1, 9 * Cin, 0, 1.0, _s())
+    torch.cuda.synchronize()
+    _close(dWs[1], dWs[0])
+    _close(dWs[2], dWs[0])
 
 
 @pytest.mark.parametrize("N,H,Cin,pre", [(97, 64, 128, False), (66, 64, 128, True), (40, 32, 256, True),
@@ -607,8 +622,8 @@ def test_conv3x3_h3_bench_launch_shape(L):
                          dx.data_ptr(), C, C, 0, None, 0, 16, None, _s())
     sp = wgrad_splits(P, C, 9 * C)
     slab = torch.full((sp, C, 9 * C), float("nan"), device="cuda")
-    L.cdm_conv3x3_wgrad_h3(gyn.data_ptr(), C, C, xn.data_ptr(), N, H, H, C, C, amg.data_ptr(), amx.data_ptr(), sp,
-                           slab.data_ptr(), _s())
+    L.cdm_conv3x3_wgrad_x16(gyn.data_ptr(), C, C, xn.data_ptr(), N, H, H, C, C, amg.data_ptr(), amx.data_ptr(), sp,
+                            slab.data_ptr(), 4, _s())
     dW = torch.empty(C, C, 3, 3, device="cuda")
     L.cdm_slab_reduce(slab.data_ptr(), sp, C, 9 * C, dW.data_ptr(), 9 * C, 1, 9, C, 0, 1.0, _s())
     torch.cuda.synchronize()

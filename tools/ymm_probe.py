@@ -28,9 +28,9 @@ amy = torch.zeros(1, device="cuda")
 
 
 def launch(with_ymm):
-    L.cdm_conv3x3_fwd_h3_ex(x.data_ptr(), N, H, H, C, C, None, None, wx.data_ptr(), am.data_ptr(), am.data_ptr() + 4,
-                            b.data_ptr(), y.data_ptr(), C, C, 0, stats.data_ptr(), C, 16, amy.data_ptr(),
-                            ymm.data_ptr() if with_ymm else None, C, s.cuda_stream)
+    L.cdm_conv3x3_fwd_x16_ex(x.data_ptr(), N, H, H, C, C, None, None, wx.data_ptr(), am.data_ptr(), am.data_ptr() + 4,
+                             b.data_ptr(), y.data_ptr(), C, C, 0, stats.data_ptr(), C, 16, amy.data_ptr(),
+                             ymm.data_ptr() if with_ymm else None, C, 4, 0, s.cuda_stream)
 
 
 for w in (False, True):
