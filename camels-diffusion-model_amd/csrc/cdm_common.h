@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define CDM_API extern "C" __attribute__((visibility("default")))
 
@@ -84,6 +85,13 @@ static __device__ __forceinline__ float gelu_grad_f(float x) {
 }
 
 static inline int cdm_status() { return (int)hipGetLastError(); }
+
+// an integer switch from the environment (dflt when unset); a switch read once per process is held in a static
+// at its call site
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

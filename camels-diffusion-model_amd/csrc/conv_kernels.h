@@ -1251,22 +1251,23 @@ constexpr int HTHREADS = 512;
 //   The fragment prefetch (the next tap's fragments are read during the current tap's MFMAs: 0.94 -> 0.84 ms) is on
 //   for NS <= 2 and off for x6, whose registers do not fit the second fragment set.
 //   XT: element type of the source x (and of PRE's y): bf16 for C4's fused-chain activations / gradients.
+// Fixed by the arithmetic: the staggered halo split (STG: waves 4-7 split + store the next chunk's halo before the
+//   last kernel row's MFMAs, waves 0-3 after them) is on for h3 and one-term, off for x3 / x6; only that order is
+//   compiled (the A/Bs: DESIGN.md section 3.3).  Tiles are always dealt XCD-aware (see the kernel).
+//   A run-time word selected the split, a static wave priority and a block start delay until commit efd0c8d
+//   (profiles/r6_ab_wave_priority.txt: neutral; the delay was off by default).
 // Dispatched: x6 <6>, x3 / h3 / wide rows <NT>, one-term bf16 <1, ONEB>, one-term forward with Cin % 32 == 0
 // <1, ONEB, DEEP>.  The kernel carried a 15-bit ablation mask until commit b6284cd (timing ablations, the 2-reads-per-
 // gap / reads-after-first-MFMA prefetch schedules, static wave priority, the halo split interleaved into the MFMAs'
 // scheduling region, 128 x 64 "tall" wave tiles, the one-term three-barrier schedule): all measured neutral or slower;
 // the figures are in DESIGN.md sections 3 and 8 and profiles/r6_conv_ablation.jsonl, the code in that commit.
-template <int NT, int WT, class EP, bool XCD_REMAP, bool ONEB = false, bool DEEP = false, class PRE = PreNone,
-          class XT = float>
+template <int NT, int WT, class EP, bool ONEB = false, bool DEEP = false, class PRE = PreNone, class XT = float>
 __global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* __restrict__ x, int H, int Cin,
                                                                       int ldx, const __bf16* __restrict__ wx3,
                                                                       int Cout, const float* amax_x,
                                                                       const float* amax_w, EP ep, PRE pre,
-                                                                      int mtiles, int tpb, int stgd = 0) {
-    // stgd: bit 0 the staggered halo split (halo_stagger), bit 1 waves 4-7 at priority 1; bits 8+: the start delay of
-    // every other block in 10 ns
-    // ticks (halo_delay: desynchronises the blocks' epilogue store bursts)
-    const int stg = stgd & 1;
+                                                                      int mtiles, int tpb) {
+    constexpr bool STG = NT == NT_H3 || NT == 1;      // the staggered halo split (see the header comment)
     constexpr int NS = XTerms<NT>::NS;
     constexpr bool PREFETCH = NS <= 2;                // register double buffer of the A / B fragments
     constexpr int HB = HBM_;                          // output pixels per tile
@@ -1293,30 +1294,16 @@ __global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    if (stgd & 2) {   // static priority for the second-dispatched half (stgd bit 1: $CDM_HALO_PRIO)
-        if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-    }
     // the block's tpb 256-pixel tiles, run one after the other: the next tile's first halo and B are fetched
     // during the current tile's last chunk, so only a block's first tile waits on HBM latency before its MFMAs.
     // XCD-aware: XCD x owns a contiguous tile range and its cnt blocks step through it together (tile
     // base + k * cnt + j), so the blocks running at one time hold consecutive tiles whose halo rows meet in L2
     // (tiles 2j, 2j+1 per block instead put the two rows shared by tiles 2j+1 and 2j+2 in different phases:
     // measured 1.6x the HBM fetch bytes)
-    int t_first = blockIdx.x * tpb, t_step = 1;
-    if constexpr (XCD_REMAP) {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, cnt = xcd < r ? q + 1 : q;
-        t_first = start * tpb + j;
-        t_step = cnt;
-    }
+    const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7;
+    const int start = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
+    const int t_first = start * tpb + (blockIdx.x >> 3), t_step = xcd < xr ? xq + 1 : xq;
     if (t_first >= mtiles) return;   // cannot happen for grid.x = ceil(mtiles / tpb); uniform per block
-    if (const unsigned dly = (unsigned)stgd >> 8; dly && ((blockIdx.x >> 3) & 1)) {
-        // every other block of each XCD starts dly x 10 ns late (s_memrealtime: 100 MHz), so that half the CUs store
-        // their tile's y while the other half compute (all blocks otherwise reach every epilogue together and the
-        // chip's write bandwidth, not the MFMAs, paces those microseconds)
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__builtin_amdgcn_s_memrealtime() - t0 < dly) __builtin_amdgcn_s_sleep(4);
-    }
     const int n0 = blockIdx.y * GBN;
     const int hw = H * WT;
     const int nchunks = Cin / 16, ngroups = nchunks * 3;
@@ -1626,9 +1613,9 @@ __global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* 
         gload_halo(morec ? cc + 1 : 0);
         compute(0, a, bcur);
         compute(1, a, bcur + BPL * XPLANE);
-        // staggered (stg): waves 4-7 split + store the next chunk before the last kernel row's MFMAs, waves 0-3 after
+        // staggered (STG): waves 4-7 split + store the next chunk before the last kernel row's MFMAs, waves 0-3 after
         // them (both buffers idle since the previous chunk's barrier)
-        const bool early = stg && __builtin_amdgcn_readfirstlane(wave) >= 4;   // wave-uniform (scalar branch)
+        const bool early = STG && __builtin_amdgcn_readfirstlane(wave) >= 4;   // wave-uniform (scalar branch)
         if (morec && early) { store_halo(Hs + (hb ^ 1) * NS * HPLANE, cc + 1); store_b((bb ^ 1) * 3 * BPL * XPLANE, bregA); }
         compute(2, a, bcur + 2 * BPL * XPLANE);
         if (morec && !early) { store_halo(Hs + (hb ^ 1) * NS * HPLANE, cc + 1); store_b((bb ^ 1) * 3 * BPL * XPLANE, bregA); }
@@ -1658,10 +1645,10 @@ __global__ __launch_bounds__(HTHREADS, 1) void conv3x3_halo_x3_kernel(const XT* 
         __syncthreads();
         bb ^= 1;
         // dy = 2: split + store the next halo (buffer idle since chunk cc-1) ahead of this group's MFMAs, so its VALU
-        // work interleaves with them; B after them.  Staggered split (stg: halo_stagger): waves 0-3 split + store the
+        // work interleaves with them; B after them.  Staggered split (STG): waves 0-3 split + store the
         // next halo after this kernel row's MFMAs, waves 4-7 before them, so each SIMD pairs one wave's VALU with its
         // partner's MFMAs (wave-uniform)
-        const bool late = stg && wave < 4;
+        const bool late = STG && wave < 4;
         // (round 6) after the block's last chunk these stores write the next tile's chunk 0 (halo and B, fetched during
         // this chunk; setup_tile moved the halo offsets) into the buffers its first chunk reads — the work the post-loop
         // stores did — so the stores need no `more chunks` condition (each condition was one more basic block splitting
@@ -1856,6 +1843,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void convT2x2_wgrad_tr_kernel(const fl
 // kx shift), so each dY fragment feeds 3 taps and X is staged once instead of three times (2.5x less LDS
 // traffic per MFMA than the retired per-tap kernel).  8 waves = 2 (co) x 4 (ci), wave tile 64 co x 32 ci x 3
 // taps (6 accumulators).  Split-K over pixel ranges; writes slab[z][co][tap*Cin+ci].
+constexpr int WG_STAGGER = 1, WG_AHEAD = 4;   // the schedule word of wgrad3x3_row_kernel (stg)
 template <int NT, int KS = 1, class PRE = PreNone, class PX = PreNone, class GT = float, class XT = float>
                                 // GT / XT: element types of dy (g and PRE's y) / of x (and PX's g): bf16 for C4's
                                 // fused-chain activations and gradients
@@ -2180,11 +2168,13 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_row_kernel(const GT* __restri
     // lock-step between the barriers.  The staging-first wave loads one K step further ahead (its registers are free
     // once it has staged), so its staging finds the data in flight since the previous step's MFMAs (round 3's form
     // loaded at the top of the step and waited out the whole HBM latency there).
-    const bool early = (stg & 1) && wave >= 4;
-    if ((stg & 2) && wave >= 4) __builtin_amdgcn_s_setprio(1);   // stg bit 1: the staging-first half at priority 1
-    // stg bit 2: the MFMA-first half also loads the K step after next as soon as it has staged (before the barrier; the
-    // default: loading at the top of the step after the barrier measured C2 46.16-46.26 -> 46.75-46.77 ms)
-    const bool ahead = UNI || early || (stg & 4);
+    // stg is 0 (lock-step: every wave MFMAs first) or WG_STAGGER | WG_AHEAD, the only two values launched.
+    const bool early = (stg & WG_STAGGER) && wave >= 4;
+    // WG_AHEAD: the MFMA-first half also loads the K step after next as soon as it has staged (before the barrier;
+    // loading at the top of the step after the barrier measured C2 46.16-46.26 -> 46.75-46.77 ms).  It stays a bit of
+    // its own: folded into one flag (ahead = UNI || stg) the compiler unswitches the non-UNI loop on it and those
+    // forms go from 148-247 VGPRs without scratch to 256 with up to 941 spilled (profiles/static_schedule_resources.txt)
+    const bool ahead = UNI || early || (stg & WG_AHEAD);
     if (kt0 < kt1) { gload(); sstore(smem); }
     if (ahead && kt0 + 1 < kt1) gload();
     __syncthreads();
@@ -2281,21 +2271,9 @@ static int halo_tpb(int mtiles, int ntiles) {
     return t < 1 ? 1 : (t > 16 ? 16 : t);
 }
 
-// the staggered halo split of the LDS-halo conv: on for h3 and (round 4, profiles/r4_ab_c4_knobs.txt) for the one-term
-// bf16 images, off for x3 / x6 ($CDM_HALO_STAGGER=0 / 1 forces it).  Same-box A/B, 2 rounds
-// (profiles/r3_ab_halo_stagger.txt): C2 (h3) train step 51.92-51.95 -> 51.34-51.44 ms
-static int halo_stagger(int nterm) {
-    static const int v = [] { const char* e = getenv("CDM_HALO_STAGGER"); return e ? atoi(e) : -1; }();
-    // + the block start delay (bits 8+, 10 ns ticks; $CDM_HALO_DELAY)
-    static const int d = [] { const char* e = getenv("CDM_HALO_DELAY"); return e ? atoi(e) : 0; }();
-    // + static priority 1 for waves 4-7 (bit 1; $CDM_HALO_PRIO, measured neutral: off, profiles/r6_ab_wave_priority.txt)
-    static const int p = [] { const char* e = getenv("CDM_HALO_PRIO"); return e ? atoi(e) : 0; }();
-    return (v >= 0 ? v : ((nterm == NT_H3 || nterm == 1) ? 1 : 0)) | (p ? 2 : 0) | (d << 8);
-}
-
 // the two-chunk-deep halo prefetch of the one-term forward halo conv ($CDM_HALO_DEEP=0: one chunk ahead)
 static int halo_deep() {
-    static const int v = [] { const char* e = getenv("CDM_HALO_DEEP"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("CDM_HALO_DEEP", 1);
     return v;
 }
 
@@ -2313,92 +2291,54 @@ static int launch_conv_halo(const XT* x, int N, int H, int Cin, int ldx, const _
     if constexpr (PRE::kind == 1) {
         if ((unsigned long long)M * (unsigned)pre.ldy * sizeof(XT) >= (1ull << 32)) return (int)hipErrorInvalidValue;
     }
-    if (!F32 && nterm != 1) return (int)hipErrorInvalidValue;
     if (tpb < 1) tpb = halo_tpb(mtiles, (Cout + GBN - 1) / GBN);
-    dim3 grid((mtiles + tpb - 1) / tpb, (Cout + GBN - 1) / GBN, 1);
-    if constexpr (WT > 64) {
-        // wide rows (C5: 128 / 256 columns): a block is 256 / WT whole rows, halo (256/WT + 2) x (WT + 2);
-        // LDS fits the two-term (h3) image only (WT 256: 2 x 2 x 774 px x 32 B + 48 KiB B = 145 KiB)
-        if constexpr (!F32) {
-            return (int)hipErrorInvalidValue;
-        } else {
-            if (nterm != NT_H3) return (int)hipErrorInvalidValue;
-            hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s,
-                               x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
-            return cdm_status();
-        }
-    } else {
-    switch (nterm) {
-        case 1:
+    const dim3 grid((mtiles + tpb - 1) / tpb, (Cout + GBN - 1) / GBN, 1);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(HTHREADS), 0, s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles,
+                           tpb);
+        return cdm_status();
+    };
+    // wide rows (C5: 128 / 256 columns): a block is 256 / WT whole rows, halo (256/WT + 2) x (WT + 2); LDS fits the
+    // two-term (h3) image only (WT 256: 2 x 2 x 774 px x 32 B + 48 KiB B = 145 KiB)
+    if constexpr (WT <= 64) {
+        if (nterm == 1) {   // one barrier per chunk (the BN-backward staging form too: profiles/r4_ab_c4_knobs.txt)
             if constexpr (!PRE::on) {
-                if (halo_deep() && Cin % 32 == 0) {
-                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, true, true, PRE, XT>),
-                                       grid, dim3(HTHREADS), 0, s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre,
-                                       mtiles, tpb, halo_stagger(nterm));
-                    break;
-                }
+                if (halo_deep() && Cin % 32 == 0) return launch(conv3x3_halo_x3_kernel<1, WT, EP, true, true, PRE, XT>);
             }
-            // one barrier per chunk (the BN-backward staging form too, since round 4: bf16 g / y,
-            // profiles/r4_ab_c4_knobs.txt)
-            hipLaunchKernelGGL((conv3x3_halo_x3_kernel<1, WT, EP, true, true, false, PRE, XT>), grid, dim3(HTHREADS), 0,
-                               s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
-            break;
-        default:
-            if constexpr (F32) {
-                if (nterm == NT_H3) {
-                    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<NT_H3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0,
-                                       s, x, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm));
-                } else if constexpr (!FUSE) {   // the x3 / x6 arithmetics: no fused eval epilogue
-                    switch (nterm) {
-                        case 3: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<3, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
-                                                   Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm)); break;
-                        case 6: hipLaunchKernelGGL((conv3x3_halo_x3_kernel<6, WT, EP, true, false, false, PRE>), grid, dim3(HTHREADS), 0, s, x, H,
-                                                   Cin, ldx, wx3, Cout, amax_x, amax_w, ep, pre, mtiles, tpb, halo_stagger(nterm)); break;
-                        default: return (int)hipErrorInvalidValue;
-                    }
-                } else {
-                    return (int)hipErrorInvalidValue;
-                }
-            } else {
-                return (int)hipErrorInvalidValue;
-            }
+            return launch(conv3x3_halo_x3_kernel<1, WT, EP, true, false, PRE, XT>);
+        }
     }
-    return cdm_status();
+    if constexpr (F32) {
+        if (nterm == NT_H3) return launch(conv3x3_halo_x3_kernel<NT_H3, WT, EP, false, false, PRE>);
+        if constexpr (WT <= 64 && !FUSE) {   // the x3 / x6 arithmetics: no fused eval epilogue
+            if (nterm == 3) return launch(conv3x3_halo_x3_kernel<3, WT, EP, false, false, PRE>);
+            if (nterm == 6) return launch(conv3x3_halo_x3_kernel<6, WT, EP, false, false, PRE>);
+        }
     }
+    return (int)hipErrorInvalidValue;
 }
 
-// LDS-halo conv of a W x W image (W in {32, 64}; 128 / 256 with the h3 arithmetic only)
+// LDS-halo conv of a W x W image (W in {32, 64}; 128 / 256 with the h3 arithmetic only, and neither for the fused eval
+// epilogue nor for the accumulating load-ahead epilogue of the dgrads)
 template <class PRE = PreNone, class XT = float, class OT = float, bool ACC = false, bool FUSE = false>
 static int launch_conv_halo_w(int W, const XT* x, int N, int H, int Cin, int ldx, const __bf16* wx3, int Cout,
                               const float* amax_x, const float* amax_w, const EpiStoreW<4, OT, ACC, FUSE>& ep, int nterm,
                               hipStream_t s, PRE pre = PRE{}) {
-    if constexpr (FUSE) {   // the fused eval epilogue: 32^2 / 64^2 maps (C2 / C4)
-        switch (W) {
-            case 32: return launch_conv_halo<32, PRE, XT, OT, ACC, FUSE>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep,
-                                                                         nterm, s, pre);
-            case 64: return launch_conv_halo<64, PRE, XT, OT, ACC, FUSE>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep,
-                                                                         nterm, s, pre);
-            default: return (int)hipErrorInvalidValue;
-        }
-    } else if constexpr (ACC) {   // the accumulating (load-ahead epilogue) variant: the dgrads at 32^2 / 64^2 only
-        switch (W) {
-            case 32: return launch_conv_halo<32, PRE, XT, OT, ACC>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm,
-                                                                   s, pre);
-            case 64: return launch_conv_halo<64, PRE, XT, OT, ACC>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm,
-                                                                   s, pre);
-            default: return (int)hipErrorInvalidValue;
-        }
-    } else {
+    auto run = [&](auto wt) {
+        return launch_conv_halo<decltype(wt)::value, PRE, XT, OT, ACC, FUSE>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w,
+                                                                             ep, nterm, s, pre);
+    };
     switch (W) {
-        case 32: return launch_conv_halo<32, PRE, XT, OT>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm, s, pre);
-        case 64: return launch_conv_halo<64, PRE, XT, OT>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm, s, pre);
-        case 128: return launch_conv_halo<128, PRE, XT, OT>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm, s, pre);
+        case 32: return run(std::integral_constant<int, 32>{});
+        case 64: return run(std::integral_constant<int, 64>{});
+        case 128:
+            if constexpr (!FUSE && !ACC) return run(std::integral_constant<int, 128>{});
+            break;
         case 256:   // the BN-backward staging registers do not fit next to the 7 halo pieces of a 256-wide row
-            if constexpr (PRE::on) return (int)hipErrorInvalidValue;
-            else return launch_conv_halo<256, PRE, XT, OT>(x, N, H, Cin, ldx, wx3, Cout, amax_x, amax_w, ep, nterm, s, pre);
-        default: return (int)hipErrorInvalidValue;
+            if constexpr (!FUSE && !ACC && !PRE::on) return run(std::integral_constant<int, 256>{});
+            break;
     }
-    }
+    return (int)hipErrorInvalidValue;
 }
 static bool halo_width_ok(int W, int nterm) {
     return W == 32 || W == 64 || ((W == 128 || W == 256) && nterm == NT_H3);

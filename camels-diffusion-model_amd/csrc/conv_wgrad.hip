@@ -1,74 +1,41 @@
 // conv3x3 weight gradient (kernel-row kernel, split-GEMM fallback): C ABI.  Kernels: conv_kernels.h.
 #include "conv_kernels.h"
 
-// the staggered wave order of the kernel-row weight gradient ($CDM_WGRAD_STAGGER, default 5 since round 6).  Round 3's
-// form was slower (C2 train step 52.11-52.42 -> 52.88-53.05 ms, C4 32.26-32.52 -> 33.38-33.61 ms, profiles/
-// r3_ab_wgrad_stagger.txt): the staging-first wave waited on the K step's loads it had just issued.  Round 6: that wave
-// loads one K step further ahead — same-box A/B, 3 rounds, C2 48.10-48.16 -> 47.02-47.09 ms and C4 25.63-25.68 ->
-// 25.24-25.27 ms per train step, slabs and sums bit-identical (profiles/r6_ab_wgrad_stagger_early.txt).  Bit 2 (default
-// value 5 = 1 | 4): the MFMA-first half, too, loads the step after next once it has staged (before the barrier rather
-// than after it): C2 46.75-46.77 -> 46.16-46.26 ms, C4 neutral (25.24-26.05 -> 25.44-25.71), bit-identical
-// (profiles/r6_ab_wgrad_ahead.txt)
+// the wave order of the kernel-row weight gradient: staggered with every wave loading one K step ahead (default), or
+// lock-step ($CDM_WGRAD_STAGGER=0, which the tests hold bit-identical to the default).  Same-box A/Bs of the staggered
+// form and of the look-ahead: profiles/r6_ab_wgrad_stagger_early.txt, r6_ab_wgrad_ahead.txt (round 3's form, slower:
+// r3_ab_wgrad_stagger.txt); the deeper and the interleaved staging that were measured and dropped:
+// r3_ab_deep_staging.txt, r3_ab_wgrad_interleave.txt.
 static int wgrad_stagger() {
-    static const int v = [] { const char* e = getenv("CDM_WGRAD_STAGGER"); return e ? atoi(e) : 5; }();
+    static const int v = env_int("CDM_WGRAD_STAGGER", 1) ? WG_STAGGER | WG_AHEAD : 0;
     return v;
 }
 
-// Two staging schedules of this kernel were measured and dropped (bit-identical outputs, same-box A/B,
-// profiles/r3_ab_deep_staging.txt, r3_ab_wgrad_interleave.txt): the K step two ahead loaded into a second register set
-// (BN coefficients moved to LDS to make room): C2 51.07-51.22 -> 51.87-52.01 ms per step, C4 neutral; the same with the
-// next step's staging interleaved into the MFMAs' scheduling region (sched_group_barrier: 1 MFMA, 2 LDS reads, 5 VALU
-// per gap): C2 49.78-49.91 -> 51.19-51.68 ms, C4 neutral.
 template <int KS, class PRE = PreNone, class PX = PreNone, class GT = float, class XT = float>
 static int launch_wgrad_row(const GT* dy, int lddy, int Cout, const XT* x, int H, int W, int Cin, int ldx, int K,
                             int sp, const float* amax_dy, const float* amax_x, float* slab, int nterm, hipStream_t st,
                             PRE pre = PRE{}, PX px = PX{}) {
     constexpr bool F32 = std::is_same<GT, float>::value && std::is_same<XT, float>::value;
     const int ktiles = K / (16 * KS), per = (ktiles + sp - 1) / sp;
-    dim3 grid((Cout / 128) * 3 * (Cin / 128) * ((ktiles + per - 1) / per));
-    if (!F32 && nterm != 1) return (int)hipErrorInvalidValue;   // bf16 activations: the one-term (C4) arithmetic only
-    if constexpr (KS == 4) {   // 64-pixel K steps: the one-term bf16 images (66 KiB of LDS), or h3 (133 KiB)
-        if constexpr (F32) {
-            if (nterm == NT_H3) {
-                hipLaunchKernelGGL((wgrad3x3_row_kernel<NT_H3, 4, PRE, PX>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H,
-                                   W, Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, px, wgrad_stagger());
-                return cdm_status();
-            }
-        }
+    const dim3 grid((Cout / 128) * 3 * (Cin / 128) * ((ktiles + per - 1) / per));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W, Cin, ldx, ktiles, per, amax_dy, amax_x,
+                           slab, pre, px, wgrad_stagger());
+        return cdm_status();
+    };
+    if constexpr (!F32) {   // bf16 activations: the one-term (C4) arithmetic only
         if (nterm != 1) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL((wgrad3x3_row_kernel<1, 4, PRE, PX, GT, XT>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W,
-                           Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, px, wgrad_stagger());
-        return cdm_status();
+        return launch(wgrad3x3_row_kernel<1, KS, PRE, PX, GT, XT>);
     } else {
-    if constexpr (!F32) {
-        hipLaunchKernelGGL((wgrad3x3_row_kernel<1, KS, PRE, PX, GT, XT>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H,
-                           W, Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, px, wgrad_stagger());
-        return cdm_status();
-    } else {
-    if constexpr (PX::kind != 0) {            // the fused X transform: the 16-bit arithmetics (h3, bf16)
-        if (nterm == NT_H3)
-            hipLaunchKernelGGL((wgrad3x3_row_kernel<NT_H3, KS, PRE, PX>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H,
-                               W, Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, px, wgrad_stagger());
-        else if (nterm == 1)
-            hipLaunchKernelGGL((wgrad3x3_row_kernel<1, KS, PRE, PX>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W,
-                               Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, px, wgrad_stagger());
-        else
-            return (int)hipErrorInvalidValue;
-        return cdm_status();
-    }
-    switch (nterm) {
-        case 1: hipLaunchKernelGGL((wgrad3x3_row_kernel<1, KS, PRE>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W, Cin, ldx,
-                                   ktiles, per, amax_dy, amax_x, slab, pre, PreNone{}, wgrad_stagger()); break;
-        case 3: hipLaunchKernelGGL((wgrad3x3_row_kernel<3, KS, PRE>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W, Cin, ldx,
-                                   ktiles, per, amax_dy, amax_x, slab, pre, PreNone{}, wgrad_stagger()); break;
-        case NT_H3: hipLaunchKernelGGL((wgrad3x3_row_kernel<NT_H3, KS, PRE>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W,
-                                       Cin, ldx, ktiles, per, amax_dy, amax_x, slab, pre, PreNone{}, wgrad_stagger()); break;
-        case 6: hipLaunchKernelGGL((wgrad3x3_row_kernel<6, KS, PRE>), grid, dim3(512), 0, st, dy, lddy, Cout, x, H, W, Cin, ldx,
-                                   ktiles, per, amax_dy, amax_x, slab, pre, PreNone{}, wgrad_stagger()); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return cdm_status();
-    }
+        // 64-pixel K steps (KS 4: one-term 66 KiB of LDS, h3 133 KiB) and the fused X transform: the 16-bit
+        // arithmetics (h3, bf16) only
+        if (nterm == NT_H3) return launch(wgrad3x3_row_kernel<NT_H3, KS, PRE, PX>);
+        if (nterm == 1) return launch(wgrad3x3_row_kernel<1, KS, PRE, PX>);
+        if constexpr (KS != 4 && PX::kind == 0) {
+            if (nterm == 3) return launch(wgrad3x3_row_kernel<3, KS, PRE, PX>);
+            if (nterm == 6) return launch(wgrad3x3_row_kernel<6, KS, PRE, PX>);
+        }
+        return (int)hipErrorInvalidValue;
     }
 }
 

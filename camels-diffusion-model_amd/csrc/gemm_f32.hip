@@ -308,8 +308,7 @@ CDM_API int cdm_convT2x2_fwd_x16(const float* x, int N, int H, int W, int Cin, i
     const int M = N * H * W, K = Cin, NN = 4 * Cout;
     EpiConvT2x2 ep{y, ldy, bias, H, W, Cout, M, NN, amax_y};
     // the two-deep prefetch form where the shape allows ($CDM_CONVT_DEEP=0: gemm_x3, read per call for A/B tests)
-    const char* dv = getenv("CDM_CONVT_DEEP");
-    if ((!dv || atoi(dv) != 0) && M % GBM == 0 && NN % GBN == 0 && K % (2 * XBK) == 0 && ldx % 4 == 0 &&
+    if (env_int("CDM_CONVT_DEEP", 1) != 0 && M % GBM == 0 && NN % GBN == 0 && K % (2 * XBK) == 0 && ldx % 4 == 0 &&
         (nterm == NT_H3 || nterm == 1)) {
         const dim3 grid(M / GBM, NN / GBN);
         const __bf16* wb = reinterpret_cast<const __bf16*>(wx);
@@ -348,8 +347,7 @@ CDM_API int cdm_convT2x2_dgrad_x16(const float* dy, int N, int H, int W, int Cou
     const int M = N * H * W, K = 4 * Cout;
     EpiStore ep{dx, lddx, 0, nullptr, 1, flags, nullptr, 0, M, Cin};
     // the two-deep prefetch form ($CDM_CONVT_DEEP=0: gemm_x3); a 16-k tile stays inside one sub-pixel (Cout % 16)
-    const char* dv = getenv("CDM_CONVT_DEEP");
-    if ((!dv || atoi(dv) != 0) && M % GBM == 0 && Cin % GBN == 0 && Cout % 16 == 0 && K % (2 * XBK) == 0 &&
+    if (env_int("CDM_CONVT_DEEP", 1) != 0 && M % GBM == 0 && Cin % GBN == 0 && Cout % 16 == 0 && K % (2 * XBK) == 0 &&
         lddy % 4 == 0 && (nterm == NT_H3 || nterm == 1)) {
         const dim3 grid(M / GBM, Cin / GBN);
         const __bf16* wb = reinterpret_cast<const __bf16*>(wx);
@@ -357,7 +355,7 @@ CDM_API int cdm_convT2x2_dgrad_x16(const float* dy, int N, int H, int W, int Cou
         // two resident blocks per CU ($CDM_CONVT_DGRAD_MINB=3: three): the 3-block form spills 36-50 VGPRs at its 168 cap;
         // 199 without spill at two — bit-identical, 219 -> 209 us (h3), 203 -> 161 us (bf16) per launch, same-box trace
         // A/B (profiles/r6_ab_convT_dgrad_minb.txt)
-        static const int mb2 = [] { const char* e = getenv("CDM_CONVT_DGRAD_MINB"); return e ? atoi(e) != 3 : 1; }();
+        static const int mb2 = env_int("CDM_CONVT_DGRAD_MINB", 2) != 3;
         if (mb2) {
             if (nterm == NT_H3)
                 hipLaunchKernelGGL((gemm_deep_kernel<NT_H3, DeepConvT2x2GatherA, EpiStore, 2>), grid, dim3(GTHREADS), 0,

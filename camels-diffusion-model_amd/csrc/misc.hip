@@ -1487,7 +1487,7 @@ CDM_API int cdm_philox_randint(int* out, int n, int lo, int hi, unsigned long lo
     return cdm_status();
 }
 static int row_kernels() {   // $CDM_ROW_KERNELS: 1 (default) the row forms of the C_in = 1 / C_out = 1 kernels, 0 flat
-    static const int v = [] { const char* e = getenv("CDM_ROW_KERNELS"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("CDM_ROW_KERNELS", 1);
     return v;
 }
 CDM_API int cdm_conv3x3_cin1_fwd(const float* x, int N, int H, int W, const float* w9, const float* bias, float* y,
@@ -1534,8 +1534,7 @@ static int launch_cout1_band(const float* z, int ldz, int N, int H, int W, int C
     const dim3 grid(N * (H / (256 / W)));
     const int hp = (256 / W + 2) * W;           // halo pixels of a band
     // 32-channel slabs on request ($CDM_COUT1_SLAB=32, read per call for A/B tests; not for 768-pixel bands: spills)
-    const char* sv = getenv("CDM_COUT1_SLAB");
-    if (C % 32 == 0 && hp <= 512 && sv && atoi(sv) == 32) {
+    if (C % 32 == 0 && hp <= 512 && env_int("CDM_COUT1_SLAB", 0) == 32) {
         if (hp <= 384)
             hipLaunchKernelGGL((conv_cout1_fwd_band_kernel<384, 32>), grid, dim3(256), 0, st, z, ldz, H, W, C, w, bias, out, gs, gt);
         else

@@ -33,7 +33,7 @@ no halo instantiation at W = 128 / 256 (halo_width_ok): the plain forward then r
 18 with nterm 1, held to the same references), the BN-ReLU forward and the BN-backward dgrad reject (one rejection case
 each), so the lists of (b) and (c) carry W = 128 for h3 only.
 
-Instantiation -> cases (conv3x3_halo_x3_kernel<NT, WT, EP, XCD, ONEB, DEEP, PRE, XT>, EP = EpiStoreW<4, OT, ACC, FUSE>):
+Instantiation -> cases (conv3x3_halo_x3_kernel<NT, WT, EP, ONEB, DEEP, PRE, XT>, EP = EpiStoreW<4, OT, ACC, FUSE>):
   <4, 32|64|128|256, <float>, PreNone>             FWD cases, nterm 4 (128: 11-13, 18; 256: 14, 15)
   <1, 32|64, <float>, ONEB, DEEP>                  FWD cases with Cin % 32 == 0 at W <= 64, nterm 1 (1, 5, 8, 17)
   <1, 32|64, <float>, ONEB>                        FWD cases with Cin in {16, 48} at W <= 64, nterm 1
