@@ -45,6 +45,12 @@ Training for guided sampling (all off by default; without them the outputs are t
                  train every sample of a step on a random image of itself under the symmetries of the maps: a flip and
                  quarter turns (d4), a periodic shift (shift) or both, drawn on the device inside the captured step; the
                  log gets a "Training options" line that names the mode.
+  --loss-weight min_snr|PATH.npy [--snr-gamma G]   --t-sampler uniform|loss [--t-buckets NB]   --t-record
+                 weight each sample's loss by its timestep (Min-SNR-gamma, G default 5, or a table of TIMESTEPS + 1
+                 weights), draw the timesteps where the weighted loss is large (importance-weighted, so the objective
+                 stays unbiased; single process only), or only keep the per-timestep record; any of them keeps the
+                 record over min(NB, TIMESTEPS) buckets of timesteps (NB default 64) on the device inside the captured
+                 step, and t_loss_record.npz (edges, count, ema_loss, prob) is written when training ends.
   --sample-steps S [--eta E] [--spacing uniform|quadratic]
                  run the sampling at the end on S of the TIMESTEPS with the strided DDIM sampler (eta 0: deterministic)
                  instead of all of them; the log lines then name steps=S, eta=E.
@@ -176,6 +182,13 @@ def main(argv=None):
                     help="clip the gradient's global L2 norm to NORM; skip steps with a non-finite gradient")
     ap.add_argument("--augment", choices=["none", "d4", "shift", "d4+shift"], default="none",
                     help="symmetry augmentation inside the step: flips / quarter turns, periodic shifts, or both")
+    ap.add_argument("--loss-weight", default=None, metavar="min_snr|PATH.npy",
+                    help="per-timestep loss weight: Min-SNR-gamma, or a table of TIMESTEPS + 1 weights >= 0")
+    ap.add_argument("--snr-gamma", type=float, default=5.0, metavar="G", help="gamma of --loss-weight min_snr")
+    ap.add_argument("--t-sampler", choices=["uniform", "loss"], default="uniform",
+                    help="how a step draws its timesteps: uniformly, or where the weighted loss is large")
+    ap.add_argument("--t-buckets", type=int, default=64, metavar="NB", help="timestep buckets of the record (1..1024)")
+    ap.add_argument("--t-record", action="store_true", help="keep the per-timestep loss record (t_loss_record.npz)")
     ap.add_argument("--resume", default=None, metavar="PATH",
                     help="write trainer_epoch_N.pt checkpoints; continue from PATH if it exists")
     ap.add_argument("--sample-steps", type=int, default=0, metavar="S",
@@ -348,6 +361,17 @@ def main(argv=None):
         ap.error(f"--sample-steps must lie in 0..TIMESTEPS = {a.timesteps}")
     if a.clip_grad is not None and not a.clip_grad > 0:
         ap.error("--clip-grad must be > 0 (inf: report the norm and skip non-finite steps only)")
+    a.t_loss = a.loss_weight is not None or a.t_sampler == "loss" or a.t_record
+    try:
+        from cdm_amd.trainer import check_t_loss
+        if a.loss_weight is not None and a.loss_weight != "min_snr":
+            a.loss_weight = np.load(a.loss_weight, allow_pickle=False)
+        check_t_loss(a.loss_weight if a.timesteps >= 1 else None, a.snr_gamma, a.t_sampler, a.t_buckets, 0.99, 10,
+                     1e-3, max(a.timesteps, 1))
+    except (OSError, ValueError) as e:
+        ap.error(f"--loss-weight / --snr-gamma / --t-sampler / --t-buckets: {e}")
+    if a.t_sampler == "loss" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--t-sampler loss is single process only (the ranks' timestep tables would diverge)")
     if a.sampler == "dpmpp" and a.sample_steps == 0:
         ap.error("--sampler dpmpp needs --sample-steps S")
     if a.sampler == "dpmpp" and a.eta != 0:
@@ -406,7 +430,8 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     model = ContextUnet(1, a.n_feat, n_cfeat, H).to(dev)
     trainer = Trainer(model, a.lr, a.timesteps, a.batch_size, seed=a.seed, ema_decay=a.ema, p_uncond=a.p_uncond,
-                      clip_grad_norm=a.clip_grad, augment=a.augment)
+                      clip_grad_norm=a.clip_grad, augment=a.augment, loss_weight=a.loss_weight, snr_gamma=a.snr_gamma,
+                      t_sampler=a.t_sampler, t_record=a.t_record, t_buckets=a.t_buckets)
     log = open(os.path.join(out_dir, "timing_and_performance.log"), "a") if rank == 0 else None
     if rank == 0 and a.augment != "none":      # without the option the log is what it was
         msg = f"Training options: p_uncond={a.p_uncond:g}, ema={a.ema}, clip_grad={a.clip_grad}, augment={a.augment}"
@@ -474,6 +499,8 @@ def main(argv=None):
         if val_log:
             np.save(os.path.join(out_dir, "val_loss_log.npy"), np.array(val_log))
         log.write(f"Total training time: {total_train:.2f} s\n")
+        if a.t_loss:                                 # the per-timestep record (rank 0's under data parallel)
+            np.savez(os.path.join(out_dir, "t_loss_record.npz"), **trainer.t_loss_report())
 
     # ------------------------------- sampling -------------------------------
     if not a.no_sample and rank == 0:

@@ -18,6 +18,9 @@ MI355X design:
     the device inside the captured step (see Trainer);
   * optional, off by default: symmetry augmentation (augment: a random flip / quarter turn and / or periodic shift per
     sample, drawn from Philox inside the step and folded into the perturb kernel's read of x0; see augment.py);
+  * optional, off by default: a per-timestep loss weight (loss_weight: Min-SNR or a table), a loss-aware timestep draw
+    (t_sampler="loss") and a per-timestep-bucket record of the raw loss (t_record), all on the device inside the
+    captured step (csrc/tloss.hip; see Trainer and DESIGN §5);
   * data parallel: one process per GPU; each rank trains on its own shard of the global batch; the
     flat gradient buffer is laid out in backward-completion order and cut into stage buckets that are
     all-reduced (RCCL over xGMI) asynchronously as soon as the engine reports a stage complete, so the
@@ -31,6 +34,7 @@ import contextlib
 import struct
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from ._lib import lib
@@ -93,7 +97,9 @@ class Trainer:
     def __init__(self, model, lrate: float, timesteps: int, batch_size: int, seed: int = 0,
                  use_graph: bool = True, group=None, broadcast_buffers: bool = True, force_ddp: bool = False,
                  ema_decay: Optional[float] = None, p_uncond: float = 0.0, clip_grad_norm: Optional[float] = None,
-                 augment: str = "none"):
+                 augment: str = "none", loss_weight=None, snr_gamma: float = 5.0, t_sampler: str = "uniform",
+                 t_record: bool = False, t_buckets: int = 64, t_ema: float = 0.99, t_warmup: int = 10,
+                 t_mix: float = 1e-3):
         """``force_ddp``: take the data-parallel path (stage-bucketed async all-reduce, rank-0 broadcasts, eager
         steps) even in a one-rank process group — RCCL readiness on a one-GPU box (tests/test_gpu_rccl.py).
         ``ema_decay``: keep ``self.ema``, an exponential moving average of the parameters, updated inside the fused
@@ -119,7 +125,29 @@ class Trainer:
         more Philox draw keyed by the step counter (``cdm_augment_draw``, sub-stream ``4 << 24``), and
         ``cdm_perturb_aug`` reads x0 through them in place of ``cdm_perturb``, both inside the captured step.  The
         noise is not transformed and the caller's batch in ``self.x0`` stays intact.  ``step(aug_ops=...)`` replaces
-        the draw for one step (eager).  Data parallel: the per-rank seed already separates the ranks' draws."""
+        the draw for one step (eager).  Data parallel: the per-rank seed already separates the ranks' draws.
+        ``loss_weight``, ``t_sampler``, ``t_record`` (DESIGN §5 has the definitions): with all three at their defaults
+        the step launches exactly what it launched without them.  ``loss_weight``: ``"min_snr"`` (the table
+        ``min_snr_weights(schedule.ab_t, snr_gamma)``) or a 1-D array of T + 1 finite numbers >= 0 (entry 0 is ignored)
+        multiplies each sample's squared error by ``w[t]``.  ``t_sampler="loss"`` draws t from a per-bucket table that
+        follows the second moment of the weighted loss (Improved DDPM's sampler over ``min(t_buckets, T)`` buckets of
+        timesteps, with the uniform share ``t_mix`` and the uniform draw until every bucket was seen ``t_warmup``
+        times) and multiplies the sample's loss by the importance weight that keeps the objective unbiased;
+        ``cdm_tsample_draw`` (sub-stream ``5 << 24``) takes ``cdm_philox_randint``'s place.  Any of the three keeps the
+        record ``self.t_rec`` [NB, 3] (device fp64 per bucket: samples seen, EMA of the raw per-sample loss, EMA of
+        the squared weighted loss; ``t_ema`` is the EMA's decay), read with ``t_loss_report()``.  Then
+        ``cdm_mse_weighted`` takes ``cdm_mse``'s place and ``cdm_tloss_record`` follows it, inside the captured step.
+        An injected ``t`` is used as given, with importance weight 1.  Data parallel: the weight and the record are
+        local to the rank; ``t_sampler="loss"`` raises (the ranks' tables would diverge)."""
+        self._t_w_host, self.NB = check_t_loss(loss_weight, snr_gamma, t_sampler, t_buckets, t_ema, t_warmup, t_mix,
+                                               int(timesteps))
+        self.t_sampler = t_sampler
+        self._t_loss = t_sampler == "loss"
+        self._tl = self._t_loss or loss_weight is not None or bool(t_record)
+        import torch.distributed as dist
+        if self._t_loss and dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1
+                                                                                  or force_ddp):
+            raise ValueError('t_sampler="loss" is single-process only: the ranks\' timestep tables would diverge')
         self._aug_mode = check_mode(augment)
         self.augment = augment
         if clip_grad_norm is not None:
@@ -136,7 +164,6 @@ class Trainer:
         self.B, self.T = int(batch_size), int(timesteps)
         self.H, self.nf, self.ncf = model.h, model.n_feat, model.n_cfeat
         self.group = group
-        import torch.distributed as dist
         self.ddp = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force_ddp)
         self.world = dist.get_world_size(group) if self.ddp else 1
         self.seed = int(seed)
@@ -202,6 +229,18 @@ class Trainer:
         self.opt_state = torch.tensor([float(lrate), 0.0, 0.0, 1.0], dtype=torch.float64, device=dev)
         self.adam_bc = adam_bias_table(*self.betas).to(dev)
         self.nonfinite = torch.zeros(1, dtype=torch.int32, device=dev)   # steps with a NaN / inf loss
+        # ---- timestep-aware loss: the weight table [T + 1], the record [NB][3] = {n, m1, m2} and, with the loss-aware
+        #      draw, its table (cdf [NB] fp64, iw_tab [NB] fp32; the uniform form until the record is warm) ----
+        self.t_w = self.t_rec = self.t_cdf = self.t_iw_tab = None
+        if self._tl:
+            self.t_alpha, self.t_warmup, self.t_mix = 1.0 - float(t_ema), int(t_warmup), float(t_mix)
+            if self._t_w_host is not None:
+                self.t_w = self._t_w_host.to(dev)
+            self.t_rec = torch.zeros(self.NB, 3, dtype=torch.float64, device=dev)
+            if self._t_loss:
+                edges = t_bucket_edges(self.T, self.NB)
+                self.t_cdf = (torch.from_numpy(edges[1:]).double() / float(self.T)).to(dev)
+                self.t_iw_tab = torch.ones(self.NB, device=dev)
         # ---- step buffers (per batch size: the epoch's ragged last batch gets its own) ----
         self.sched = Schedule(self.T, dev)
         self.sc = torch.empty(2 * self.nf, device=dev)
@@ -223,7 +262,8 @@ class Trainer:
     def _use(self, B: int):
         b = self._bufs.get(B)
         if b is None:
-            b = self._bufs[B] = _StepBufs(self.eng, B, self.H, self.ncf, self.dev, aug=self._aug_mode != 0)
+            b = self._bufs[B] = _StepBufs(self.eng, B, self.H, self.ncf, self.dev, aug=self._aug_mode != 0,
+                                          tl=self._tl, t_loss=self._t_loss)
         self.cur = b
         return b
 
@@ -273,6 +313,40 @@ class Trainer:
             self.skipped.zero_()
         return n
 
+    def _need_t_rec(self):
+        if not self._tl:
+            raise RuntimeError("this Trainer keeps no per-timestep record (loss_weight=None, t_sampler='uniform', "
+                               "t_record=False)")
+
+    def set_t_options(self, t_ema: Optional[float] = None, t_warmup: Optional[int] = None,
+                      t_mix: Optional[float] = None):
+        """New record decay / warm-up count / uniform share from the next step on.  They are plain launch arguments of
+        ``cdm_tloss_record``: the captured step is dropped and captured again."""
+        self._need_t_rec()
+        check_t_loss(None, 1.0, "uniform", 1, 1.0 - self.t_alpha if t_ema is None else t_ema,
+                     self.t_warmup if t_warmup is None else t_warmup, self.t_mix if t_mix is None else t_mix, 1)
+        if t_ema is not None:
+            self.t_alpha = 1.0 - float(t_ema)
+        if t_warmup is not None:
+            self.t_warmup = int(t_warmup)
+        if t_mix is not None:
+            self.t_mix = float(t_mix)
+        self.graph = None
+
+    def t_loss_report(self) -> Dict[str, np.ndarray]:
+        """The per-bucket record as host arrays: ``edges`` [NB + 1] (bucket k holds the timesteps edges[k] + 1 ..
+        edges[k + 1]), ``count`` [NB] (samples seen), ``ema_loss`` [NB] (EMA of the raw per-sample loss; 0 where
+        count is 0) and ``prob`` [NB] (the probability the next draw gives the bucket: q_k of the loss-aware table, or
+        n_k / T with the uniform draw).  One host sync: call it once per epoch, not per step."""
+        self._need_t_rec()
+        rec = self.t_rec.cpu().numpy()
+        edges = t_bucket_edges(self.T, self.NB)
+        if self._t_loss:
+            prob = t_table(rec, self.T, self.NB, self.t_warmup, self.t_mix)[2]
+        else:
+            prob = np.diff(edges).astype(np.float64) / float(self.T)
+        return {"edges": edges, "count": rec[:, 0].astype(np.int64), "ema_loss": rec[:, 1].copy(), "prob": prob}
+
     def check_finite(self, reset: bool = True) -> int:
         """Number of steps since the last check whose loss was NaN / inf (SURVEY §5 failure guard).  One host sync:
         call it once per epoch, not per step."""
@@ -320,7 +394,7 @@ class Trainer:
         optimizer state [lr, step, ...], the Philox step counter and the scalar settings the draws depend on."""
         def cpu(t):
             return t.detach().cpu().clone()
-        return {
+        out = {
             "version": 1,
             "model": {k: cpu(v) for k, v in self.model.state_dict().items()},
             "layout": list(self.offsets),
@@ -332,6 +406,14 @@ class Trainer:
             "clip_grad_norm": float(self.max_norm.item()) if self.clip else None, "skipped": cpu(self.skipped),
             "augment": self.augment,
         }
+        if self._tl:               # with the options off the keys are those of a trainer from before them
+            out["t_loss"] = {
+                "rec": cpu(self.t_rec), "cdf": None if self.t_cdf is None else cpu(self.t_cdf),
+                "iw_tab": None if self.t_iw_tab is None else cpu(self.t_iw_tab),
+                "w": None if self.t_w is None else cpu(self.t_w), "t_sampler": self.t_sampler, "t_buckets": int(self.NB),
+                "alpha": float(self.t_alpha), "t_warmup": int(self.t_warmup), "t_mix": float(self.t_mix),
+            }
+        return out
 
     def load_state_dict(self, sd: Dict[str, object]):
         """Continue from ``state_dict()`` output.  Every tensor is copied into the buffer the trainer already holds
@@ -347,6 +429,21 @@ class Trainer:
         if sd.get("augment", "none") != self.augment:               # checkpoints from before the option: "none"
             raise ValueError(f"the checkpoint was written with augment={sd.get('augment', 'none')!r} and the trainer "
                              f"was built with augment={self.augment!r}")
+        tl = sd.get("t_loss")                                       # checkpoints from before the option: off
+        if (tl is not None) != self._tl:
+            raise ValueError("the checkpoint keeps a per-timestep loss record and the trainer was built without "
+                             "loss_weight, t_sampler='loss' or t_record" if not self._tl else
+                             "the trainer keeps a per-timestep loss record and the checkpoint has none")
+        if tl is not None:
+            if tl["t_sampler"] != self.t_sampler or int(tl["t_buckets"]) != self.NB:
+                raise ValueError(f"the checkpoint was written with t_sampler={tl['t_sampler']!r} over "
+                                 f"{int(tl['t_buckets'])} buckets and the trainer was built with "
+                                 f"t_sampler={self.t_sampler!r} over {self.NB}")
+            if (tl["w"] is None) != (self.t_w is None) or \
+                    (tl["w"] is not None and not torch.equal(tl["w"].cpu(), self.t_w.cpu())):
+                raise ValueError("the checkpoint was written with another loss_weight than the trainer was built with")
+            if tuple(tl["rec"].shape) != (self.NB, 3):
+                raise ValueError("t_loss.rec: size mismatch")
         if list(sd["layout"]) != list(self.offsets):
             raise ValueError("checkpoint holds a different parameter list than this model")
         own = self.model.state_dict()
@@ -375,6 +472,14 @@ class Trainer:
                 self.skipped.copy_(sd["skipped"])
             else:
                 self.skipped.zero_()
+            if tl is not None:
+                self.t_rec.copy_(tl["rec"])
+                if self._t_loss:
+                    self.t_cdf.copy_(tl["cdf"]); self.t_iw_tab.copy_(tl["iw_tab"])
+        if tl is not None and (float(tl["alpha"]), int(tl["t_warmup"]), float(tl["t_mix"])) != \
+                (self.t_alpha, self.t_warmup, self.t_mix):
+            self.t_alpha, self.t_warmup, self.t_mix = float(tl["alpha"]), int(tl["t_warmup"]), float(tl["t_mix"])
+            self.graph = None                # launch arguments of the captured step
         self.steps = int(sd["steps"])
         if int(sd["seed"]) != self.seed or float(sd["p_uncond"]) != self.p_uncond:
             self.seed, self.p_uncond = int(sd["seed"]), float(sd["p_uncond"])
@@ -389,7 +494,11 @@ class Trainer:
         seed = self.seed * 1000003 + (self._rank() << 20)
         if self._inject is None:
             lb.cdm_philox_normal(_p(sb.noise), B * HW, seed, 0, _p(self.ctr), s)
-            lb.cdm_philox_randint(_p(sb.t_int), B, 1, self.T, seed, 1 << 24, _p(self.ctr), s)
+            if self._t_loss:       # the loss-aware draw: t and its importance weight from the table of the step before
+                lb.cdm_tsample_draw(_p(sb.t_int), _p(sb.iw), B, self.T, self.NB, _p(self.t_cdf), _p(self.t_iw_tab),
+                                    seed, 5 << 24, _p(self.ctr), s)
+            else:
+                lb.cdm_philox_randint(_p(sb.t_int), B, 1, self.T, seed, 1 << 24, _p(self.ctr), s)
             lb.cdm_philox_uniform(_p(self.sc), 2 * nf, -1.0, 1.0, seed, 2 << 24, _p(self.ctr), s)
         else:                      # parity mode: caller-provided draws (eager only)
             noise, t_int, sc = self._inject[:3]
@@ -417,8 +526,17 @@ class Trainer:
         self.eng.repack(P, True, s)
         eps = self.eng.forward(sb.ws, P, sb.xpert, sb.t_in, c_in, self.sc[:nf], self.sc[nf:], B, s)
         gnum = float(B * HW) if self.grad_numel is None else float(self.grad_numel)
-        lb.cdm_mse(_p(eps), _p(sb.noise), B * HW, gnum, _p(sb.deps), _p(self.partial), self.nb, _p(self.loss),
-                   _p(self.grads["out.3.bias"]), _p(self.nonfinite), s)
+        if self._tl:               # per-row sums, the weighted loss and gradient, then the record (and the table)
+            iw = sb.iw if self._t_loss and self._inject is None else None     # an injected t: importance weight 1
+            lb.cdm_mse_weighted(_p(eps), _p(sb.noise), B, HW, _p(sb.t_int), _p(self.t_w), _p(iw), gnum, _p(sb.deps),
+                                _p(sb.row_sq), _p(sb.row_g), _p(self.loss), _p(self.grads["out.3.bias"]),
+                                _p(self.nonfinite), s)
+            lb.cdm_tloss_record(_p(sb.row_sq), _p(sb.t_int), _p(self.t_w), B, HW, self.T, self.NB, self.t_alpha,
+                                _p(self.t_rec), 1 if self._t_loss else 0, self.t_warmup, self.t_mix, _p(self.t_cdf),
+                                _p(self.t_iw_tab), s)
+        else:
+            lb.cdm_mse(_p(eps), _p(sb.noise), B * HW, gnum, _p(sb.deps), _p(self.partial), self.nb, _p(self.loss),
+                       _p(self.grads["out.3.bias"]), _p(self.nonfinite), s)
         hooks = [h for h in (self.bucketer.stage_ready if self.ddp else None, self.stage_hook) if h is not None]
         hook = (lambda name: [h(name) for h in hooks]) if hooks else None
         self.eng.backward(sb.ws, P, sb.deps, self.grads, s, out3_bias_done=True, on_stage=hook)
@@ -523,6 +641,86 @@ def shard_epoch(order: torch.Tensor, batch_size: int, world: int, rank: int):
     return out
 
 
+TLOSS_MAX_BUCKETS = 1024           # CDM_TLOSS_MAX_BUCKETS (include/cdm_hip.h)
+
+
+def t_bucket_edges(T: int, NB: int) -> np.ndarray:
+    """edges [NB + 1] int64 of the timestep buckets: edge_k = (k T) // NB; bucket k holds edge_k + 1 .. edge_{k+1}."""
+    return (np.arange(NB + 1, dtype=np.int64) * int(T)) // int(NB)
+
+
+def min_snr_weights(ab_t, gamma: float = 5.0) -> torch.Tensor:
+    """The Min-SNR-gamma weight of the eps-prediction loss under this project's perturbation
+    x_t = sqrt(ab_t) x + (1 - ab_t) noise: w_t = min(SNR_t, gamma) / SNR_t = min(1, gamma / SNR_t) with
+    SNR_t = ab_t / (1 - ab_t)^2, evaluated in fp64 and rounded to fp32 once; w_0 = 0 (unused).  [T + 1] fp32, CPU."""
+    if not float(gamma) > 0.0:
+        raise ValueError(f"snr_gamma must be > 0, got {gamma}")
+    ab = torch.as_tensor(ab_t).detach().cpu().double().numpy().reshape(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        om = 1.0 - ab
+        snr = ab / (om * om)
+        w = np.minimum(1.0, float(gamma) / snr)
+    w[0] = 0.0
+    return torch.from_numpy(w.astype(np.float32))
+
+
+def check_t_loss(loss_weight, snr_gamma, t_sampler, t_buckets, t_ema, t_warmup, t_mix, T: int):
+    """Validates the timestep-loss options of Trainer (ValueError) without touching a device; returns (the weight
+    table [T + 1] fp32 on the CPU or None, NB = min(t_buckets, T))."""
+    if t_sampler not in ("uniform", "loss"):
+        raise ValueError(f't_sampler must be "uniform" or "loss", got {t_sampler!r}')
+    if not float(snr_gamma) > 0.0:
+        raise ValueError(f"snr_gamma must be > 0, got {snr_gamma}")
+    if int(t_buckets) != t_buckets or not 1 <= int(t_buckets) <= TLOSS_MAX_BUCKETS:
+        raise ValueError(f"t_buckets must lie in 1..{TLOSS_MAX_BUCKETS}, got {t_buckets}")
+    if not 0.0 <= float(t_ema) < 1.0:
+        raise ValueError(f"t_ema must lie in [0, 1), got {t_ema}")
+    if int(t_warmup) != t_warmup or int(t_warmup) < 1:
+        raise ValueError(f"t_warmup must be an integer >= 1, got {t_warmup}")
+    if not 0.0 < float(t_mix) <= 1.0:
+        raise ValueError(f"t_mix must lie in (0, 1], got {t_mix}")
+    w = None
+    if isinstance(loss_weight, str):
+        if loss_weight != "min_snr":
+            raise ValueError(f'loss_weight must be None, "min_snr" or a table of T + 1 weights, got {loss_weight!r}')
+        w = min_snr_weights(Schedule(T, "cpu").ab_t, snr_gamma)
+    elif loss_weight is not None:
+        w = torch.as_tensor(loss_weight).detach().cpu()
+        if w.dim() != 1 or w.numel() != T + 1:
+            raise ValueError(f"loss_weight must be 1-D with T + 1 = {T + 1} entries, got shape {tuple(w.shape)}")
+        if w.is_complex() or w.dtype == torch.bool:
+            raise ValueError(f"loss_weight must hold real numbers, got {w.dtype}")
+        w = w.double()
+        if not bool(torch.isfinite(w[1:]).all()) or bool((w[1:] < 0).any()):
+            raise ValueError("loss_weight must be finite and >= 0")
+        w = w.float()
+        if not bool(torch.isfinite(w[1:]).all()):
+            raise ValueError("loss_weight must be finite in fp32")
+        w[0] = 0.0                   # entry 0 is ignored: no timestep reads it
+    return w, min(int(t_buckets), int(T))
+
+
+def t_table(rec: np.ndarray, T: int, NB: int, warmup: int, mix: float):
+    """The loss-aware timestep table cdm_tloss_record (mode 1) builds from the record rec [NB, 3] = {n, m1, m2}, on the
+    host in the same fp64 operations: (cdf [NB] fp64, iw_tab [NB] fp32, q [NB] fp64 the bucket probabilities)."""
+    edges = t_bucket_edges(T, NB)
+    nk = np.diff(edges).astype(np.float64)
+    rec = np.asarray(rec, dtype=np.float64)
+    r = np.sqrt(rec[:, 2])
+    S = np.float64(0.0)
+    for v in r:
+        S = S + v
+    if rec[:, 0].min() < warmup or not np.isfinite(S) or not S > 0.0:
+        return edges[1:].astype(np.float64) / np.float64(T), np.ones(NB, np.float32), nk / np.float64(T)
+    q = ((np.float64(1.0) - np.float64(mix)) * r) / S + (np.float64(mix) * nk) / np.float64(T)
+    cdf = np.empty(NB, np.float64)
+    run = np.float64(0.0)
+    for k in range(NB):
+        run = run + q[k]
+        cdf[k] = run
+    return cdf, (nk / (np.float64(T) * q)).astype(np.float32), q
+
+
 GRAD_SUMSQ_MAX_PARTIALS = 2048     # CDM_GRAD_SUMSQ_MAX_PARTIALS (include/cdm_hip.h): doubles cdm_adam_clipped may write
 
 
@@ -552,7 +750,7 @@ def adam_bias_table(beta1: float, beta2: float, n: int = 40960) -> torch.Tensor:
 class _StepBufs:
     """Device buffers of one training step at batch size B (engine workspace included)."""
 
-    def __init__(self, eng, B: int, H: int, ncf: int, dev, aug: bool = False):
+    def __init__(self, eng, B: int, H: int, ncf: int, dev, aug: bool = False, tl: bool = False, t_loss: bool = False):
         HW = H * H
         self.B = B
         self.x0 = torch.zeros(B, H, H, device=dev)
@@ -566,4 +764,9 @@ class _StepBufs:
         self.keep = torch.ones(B, dtype=torch.int32, device=dev)     # its mask: 0 = dropped
         if aug:
             self.ops = torch.zeros(B, 3, dtype=torch.int32, device=dev)   # (g, dy, dx) per sample (augment != "none")
+        if tl:                                                       # per-row sums of the weighted MSE (timestep loss)
+            self.row_sq = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.row_g = torch.zeros(B, dtype=torch.float64, device=dev)
+        if t_loss:
+            self.iw = torch.ones(B, device=dev)                      # importance weights of the loss-aware draw
         self.ws = eng.workspace(B, True)

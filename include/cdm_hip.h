@@ -662,6 +662,53 @@ int cdm_augment_draw(int* ops, int B, int H, int mode, unsigned long long seed, 
 int cdm_perturb_aug(const float* x, const int* ops, const float* noise, const int* t, const int* cur_i,
                     long long nstride, const float* sab, const float* omab, int N, int HW, int H, int T, float* out,
                     float* tin, void* stream);
+/* Timestep-aware training loss (Trainer(loss_weight=..., t_sampler=..., t_record=...), not in the reference;
+ * csrc/tloss.hip).  The timesteps 1..T fall into NB <= CDM_TLOSS_MAX_BUCKETS buckets: edge_k = (k T) / NB
+ * in integer arithmetic for k = 0..NB, bucket k = edge_k + 1 .. edge_{k+1}, n_k = edge_{k+1} - edge_k >= 1 (NB <= T);
+ * the bucket of t is (t NB - 1) / T.  None of the three synchronises or allocates.
+ * cdm_tsample_draw: t [B] int and iw [B] fp32 from cdf [NB] fp64 and iw_tab [NB] fp32.  u0, u1 = elements 2b, 2b + 1
+ * of what cdm_philox_uniform(out, 2 B, 0, 1, seed, sub, sub_dev) writes; k = the count of j in 0..NB-2 with
+ * cdf[j] <= (double)u0 (cdf[NB - 1] is never read: a u0 of exactly 1 lands in bucket NB - 1);
+ * t[b] = edge_k + 1 + min(n_k - 1, (int)((float)n_k * u1)) in fp32; iw[b] = iw_tab[k].
+ * hipErrorInvalidValue, nothing launched: a pointer (other than sub_dev) null; B, T or NB < 1; NB > T;
+ * NB > CDM_TLOSS_MAX_BUCKETS. */
+#define CDM_TLOSS_MAX_BUCKETS 1024
+int cdm_tsample_draw(int* t, float* iw, int B, int T, int NB, const double* cdf, const float* iw_tab,
+                     unsigned long long seed, unsigned int sub, const int* sub_dev, void* stream);
+/* cdm_mse with a weight per row: pred, noise, dpred [B][HW]; omega_b = w_tab[t[b]] * iw[b], one fp32 product (w_tab
+ * [T + 1] fp32 and iw [B] fp32 may each be null and then count as 1; t [B] int is read only with w_tab, and t[b] must
+ * index it: the call cannot check that);
+ *   d = pred - noise                                  fp32
+ *   dpred[b][p] = d * ((float)(2 / grad_numel) * omega_b)      the factor one fp32 product; both tables null: the factor
+ *                                                     is (float)(2 / grad_numel) and dpred has cdm_mse's bits
+ *   row_sq[b] = sum_p (double)d (double)d,  row_g[b] = sum_p (double)dpred[b][p]       fp64 [B] each
+ *   loss = (float)((sum_b (double)omega_b * row_sq[b]) / ((double)B * (double)HW)),  dbias = (float)(sum_b row_g[b])
+ * the last two by one thread over b = 0..B-1 in order, one IEEE fp64 operation per step; nonfinite (optional) += 1
+ * when the loss is NaN / inf.  One block of 256 threads per row; any HW >= 1 and 4-byte aligned bases: float4 loads /
+ * stores on the 16-byte aligned body of a row when the three rows agree mod 16, scalar head and tail; per-thread fp64
+ * sums over a fixed element set, a wave64 butterfly, a fixed-order fold: two runs give the same bits; no atomics.
+ * hipErrorInvalidValue, nothing launched: pred, noise, dpred, row_sq or row_g null; w_tab without t; B or HW < 1;
+ * grad_numel <= 0. */
+int cdm_mse_weighted(const float* pred, const float* noise, int B, int HW, const int* t, const float* w_tab,
+                     const float* iw, double grad_numel, float* dpred, double* row_sq, double* row_g, float* loss_out,
+                     float* dbias_out, int* nonfinite, void* stream);
+/* The per-bucket record of the raw loss and the loss-aware timestep table.  rec [NB][3] fp64 = {n, m1, m2}: samples
+ * seen, EMA of l, EMA of y = (w_tab[t] l)^2 (w_tab null: l^2; the importance weight is not part of it).  One thread,
+ * for b = 0..B-1 in order, every fp64 operation one IEEE operation (no contraction):
+ *   l = row_sq[b] / (double)HW;  a non-finite l, or a t[b] outside 1..T, leaves the record alone
+ *   k = bucket of t[b];  wl = (double)w_tab[t[b]] * l;  y = wl * wl
+ *   n == 0:  m1 = l, m2 = y;   else  m1 = m1 + alpha * (l - m1),  m2 = m2 + alpha * (y - m2);   then n = n + 1
+ * mode 0 stops here (cdf, iw_tab unread and unwritten: they may be null).  mode 1 rebuilds cdf [NB] fp64 and iw_tab
+ * [NB] fp32 from the record alone: S = the in-order sum of sqrt(m2_k);
+ *   uniform form, while min_k n < warmup, or S is not finite or not > 0:
+ *     cdf[k] = (double)edge_{k+1} / (double)T,  iw_tab[k] = 1.0f
+ *   else  q_k = ((1 - mix) * sqrt(m2_k)) / S + (mix * n_k) / T;  cdf[k] = the in-order running sum of q;
+ *     iw_tab[k] = (float)(n_k / (T * q_k))        (n_k here the bucket's size, T and n_k as doubles)
+ * hipErrorInvalidValue, nothing launched: row_sq, t or rec null; B, HW, T or NB < 1; NB > T;
+ * NB > CDM_TLOSS_MAX_BUCKETS; alpha outside (0, 1]; mode outside 0..1; mode 1 with cdf or iw_tab null, warmup < 1 or
+ * mix outside (0, 1]. */
+int cdm_tloss_record(const double* row_sq, const int* t, const float* w_tab, int B, int HW, int T, int NB, double alpha,
+                     double* rec, int mode, int warmup, double mix, double* cdf, float* iw_tab, void* stream);
 /* weight repacking (+ eval-mode BatchNorm folding) */
 /* kc = 0: K order tap-major (k = tap*C + ci); kc = 16: channel-chunk-major (k = ((ci/16)*9 + tap)*16 + ci%16),
  * the order cdm_conv3x3_fwd(kc = 16) consumes (wdg is chunked over Cout).  ConvTranspose packing: */
