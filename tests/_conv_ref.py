@@ -174,7 +174,10 @@ def epilogue(v, flags, old=None, bias=None, to_bf16=False):
 
 
 def tile_stats(y):
-    """y [..., C] (pixels a multiple of 128) -> (sums, sums of squares), each [pixels / 128, C]"""
+    """y [..., C] -> (sums, sums of squares), each [ceil(pixels / 128), C]; a partial last tile sums the rows that exist"""
+    y = y.reshape(-1, y.shape[-1])
+    if y.shape[0] % 128:
+        y = np.concatenate([y, np.zeros((-y.shape[0] % 128, y.shape[1]))])
     t = y.reshape(-1, 128, y.shape[-1])
     return t.sum(1), (t * t).sum(1)
 

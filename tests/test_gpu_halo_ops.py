@@ -154,7 +154,7 @@ def mode_of(data, nterm):
 def check_stats(stats, stats_ld, got, Cout, mode, what):
     """stats[tile][0 | 1][stats_ld] of the stored values: sums exact on exact data (else chain_bound(128, sum|v|)), sums
     of squares chain_bound(128, sum v^2) per 128-pixel tile (the epilogue's fp32 v v is inexact); pads untouched"""
-    tiles = got.reshape(-1, Cout).shape[0] // 128
+    tiles = -(-got.reshape(-1, Cout).shape[0] // 128)      # a partial last tile: the rows that exist
     a = Hh(stats).reshape(tiles, 2, stats_ld)
     assert (a[:, :, Cout:] == SENT).all(), f"{what}: stats pad written"
     s_ref, q_ref = R.tile_stats(got.reshape(-1, Cout))

@@ -4,7 +4,10 @@ Tolerance: fp32 MFMA vs CPU fp32 with different summation order -> |err| <= 2e-5
 
 The fused forms of the LDS-halo conv and of the kernel-row weight gradient (BN-ReLU / BN-backward staging, accumulate and
 relu epilogues, statistics and max / min keys, the eval epilogues, bf16 storage, shapes off the workload's) are held to
-fp64 references, bit for bit on exact data, in tests/test_gpu_halo_ops.py.
+fp64 references, bit for bit on exact data, in tests/test_gpu_halo_ops.py.  The kernels tested here (csrc/gemm_f32.hip:
+the ConvT 2x2 ops with the two-deep prefetch and transposed-read kernels, the fp32 3x3 conv and its split-bf16 siblings,
+the dense GEMMs, cdm_slab_reduce) are held to fp64 references the same way, with ld > C, nonzero offsets, sentinels,
+H != W and every split's slab on its own, in tests/test_gpu_gemm_ops.py.
 """
 import os
 
