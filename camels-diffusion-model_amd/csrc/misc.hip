@@ -1320,7 +1320,7 @@ __global__ __launch_bounds__(256) void clip_prep_kernel(const double* partial, i
 
 // Context dropout for classifier-free guidance: c_out[b][:] = u[b] < p_drop ? 0 : c[b][:], u[b] element b of the
 // stream philox_uniform_kernel(out, B, 0, 1, seed, sub, sub_dev) writes (lo + (hi - lo) u01 is u01 itself there).
-// keep (optional) [B]: 1 where the row was kept.
+// u01 lies in (0, 1], so p_drop == 1 is its own case and drops every row.  keep (optional) [B]: 1 where the row was kept.
 __global__ void context_drop_kernel(const float* c, int B, int ncf, float p_drop, unsigned long long seed, uint32_t sub,
                                     const int* sub_dev, float* c_out, int* keep) {
     if (sub_dev) sub += (uint32_t)*sub_dev;
@@ -1330,7 +1330,7 @@ __global__ void context_drop_kernel(const float* c, int B, int ncf, float p_drop
         const U4 r = philox((uint32_t)(b >> 2), 0u, sub, 0x0417u, (uint32_t)seed, (uint32_t)(seed >> 32));
         const int j = b & 3;
         const float u = u01(j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w)));
-        const bool drop = u < p_drop;
+        const bool drop = u < p_drop || p_drop >= 1.0f;   // u01 reaches 1.0f: p_drop == 1 must not keep such a row
         c_out[i] = drop ? 0.f : c[i];
         if (keep && f == 0) keep[b] = drop ? 0 : 1;
     }
@@ -1471,17 +1471,25 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 // ------------------------------------------ C ABI ------------------------------------------------
 CDM_API int cdm_philox_normal(float* out, long long n, unsigned long long seed, unsigned int sub, const int* sub_dev,
                               void* stream) {
+    if (n < 0 || (n > 0 && !out)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
     hipLaunchKernelGGL(philox_normal_kernel, dim3(nblocks((n + 3) / 4)), dim3(256), 0, S(stream), out, n, seed, sub, sub_dev);
     return cdm_status();
 }
 CDM_API int cdm_philox_uniform(float* out, long long n, float lo, float hi, unsigned long long seed, unsigned int sub,
                                const int* sub_dev, void* stream) {
+    if (n < 0 || (n > 0 && !out) || !(lo <= hi) || !(lo > -__builtin_inff()) || !(hi < __builtin_inff()))
+        return (int)hipErrorInvalidValue;                         // NaN fails lo <= hi
+    if (n == 0) return 0;
     hipLaunchKernelGGL(philox_uniform_kernel, dim3(nblocks((n + 3) / 4)), dim3(256), 0, S(stream), out, n, lo, hi, seed, sub,
                        sub_dev);
     return cdm_status();
 }
 CDM_API int cdm_philox_randint(int* out, int n, int lo, int hi, unsigned long long seed, unsigned int sub,
                                const int* sub_dev, void* stream) {
+    if (n < 0 || (n > 0 && !out) || hi < lo || (long long)hi - lo >= 0x7fffffffll)   // hi - lo + 1 must fit an int
+        return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
     hipLaunchKernelGGL(philox_randint_kernel, dim3((n + 255) / 256), dim3(256), 0, S(stream), out, n, lo, hi, seed, sub,
                        sub_dev);
     return cdm_status();

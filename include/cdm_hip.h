@@ -582,8 +582,34 @@ int cdm_flow_step(float* x, const float* eps, const float* dx, int n, int H, con
 int cdm_flow_finish(const float* x, int n, int H, double log_abT, const double* acc, double* prior, double* logp,
                     void* stream);
 /* randn_like/ randint / the per-forward random 1x1 shortcut draw (diffusion_utilities.py:54), on-device Philox.
- * The stream id is sub (+ *sub_dev when given: a device counter advanced by cdm_counter_add, so a captured
- * step draws fresh numbers on every replay). */
+ * The stream id is sub (+ *sub_dev when given, mod 2^32: a device counter advanced by cdm_counter_add, so a captured
+ * step draws fresh numbers on every replay).  Callers that give each consumer the sub-stream k << 24 plus a step
+ * counter keep their streams disjoint for fewer than 2^24 steps.
+ * The contract of every device draw (csrc/sampler_parts.h; tests/_rng_ref.py restates it on the host and
+ * tests/test_gpu_rng.py holds the device to it):
+ *   words   Philox4x32-10 (Random123's multipliers, key schedule and word order) under the key words
+ *           ((uint32)seed, seed >> 32), of the counter (c0, c1, c2, c3) with c3 the domain word:
+ *             0x5EED  normal:  (q, q >> 32, sub, 0x5EED); element 4 q + 0 / 1 = r cos / r sin of the words (x, y),
+ *                      4 q + 2 / 3 of (z, w); r = sqrtf(-2 logf(u1)), angle 6.283185307179586f * u2, (u1, u2) = u01 of
+ *                      the pair.  cdm_philox_normal and every in-kernel z / xi / zeta.
+ *             0x0417  uniform: (q, q >> 32, sub, 0x0417); element 4 q + j = lo + (hi - lo) u01(word j) in fp32 (the
+ *                      product and the sum may be one fma; at (0, 1) it is u01 itself).  cdm_philox_uniform,
+ *                      cdm_context_drop, cdm_augment_draw, cdm_tsample_draw, cdm_flow_probe.
+ *             0xA11C  randint: (i, 0x71, sub, 0xA11C); element i = lo + (((x << 32) | y) % (hi - lo + 1)).
+ *   u01(v) = ((float)(v >> 8) + 0.5f) * 2^-24 in fp32.  Range (0, 1], not (0, 1): for v >> 8 >= 2^23 the + 0.5f is a
+ *           tie and rounds to even, so v >> 8 == 0xFFFFFF gives exactly 1.0f (and the upper half of the range has half
+ *           the resolution).  Never 0: the smallest value is 2^-25.  cdm_philox_uniform(out, 1, 0, 1, 0, 1543363)
+ *           writes 1.0f.
+ *   keys    the samplers' draws are keyed by seed ^ *seed_dev, XOR one of four key-domain constants, each the big-endian
+ *           ASCII of its name and nothing else:
+ *             (none)                                   z of cdm_denoise and cdm_ddim_step, stream i (the timestep)
+ *             0x706F735F73746570 "pos_step"  STEP_NOISE_DOMAIN   z of cdm_ddim_step_pos / _guided, stream k
+ *             0x6B6E6F776E5F7869 "known_xi"  KNOWN_NOISE_DOMAIN  xi of cdm_mask_blend (stream fresh ? j : 0) and
+ *                                                                of cdm_mask_blend_jump (stream fresh ? p : 0)
+ *             0x6A756D707A657461 "jumpzeta"  JUMP_NOISE_DOMAIN   zeta of cdm_mask_blend_jump, stream p
+ *             0x666C6F7770726F62 "flowprob"  FLOW_PROBE_DOMAIN   the probes of cdm_flow_probe / cdm_flow_step, stream p
+ * hipErrorInvalidValue, nothing launched: n < 0; out null with n > 0; cdm_philox_uniform with lo or hi not finite or
+ * hi < lo; cdm_philox_randint with hi < lo or hi - lo + 1 beyond an int.  n == 0 returns 0 without a launch. */
 int cdm_philox_normal(float* out, long long n, unsigned long long seed, unsigned int sub, const int* sub_dev,
                       void* stream);
 int cdm_philox_uniform(float* out, long long n, float lo, float hi, unsigned long long seed, unsigned int sub,
@@ -637,7 +663,9 @@ int cdm_adam_clipped(float* p, const float* g, float* m, float* v, float* ema, l
                      void* stream);
 /* context dropout (training for classifier-free guidance): u[b] = element b of what
  * cdm_philox_uniform(out, B, 0, 1, seed, sub, sub_dev) writes; c_out[b][:] = u[b] < p_drop ? 0 : c[b][:] for c, c_out
- * [B][ncf]; keep (optional, int [B]) = 0 where the row was dropped, else 1.  c_out must not be c.
+ * [B][ncf]; keep (optional, int [B]) = 0 where the row was dropped, else 1.  c_out must not be c.  u lies in (0, 1]
+ * (u01 reaches 1.0f), so p_drop == 1 is a case of its own: it drops every row, whatever u.  Every p_drop < 1 is the
+ * plain comparison, so p_drop = 0.99999994f keeps a row whose u is 1.0f.
  * hipErrorInvalidValue: p_drop outside [0, 1] or NaN, B < 1, ncf < 1, c or c_out null, c_out == c. */
 int cdm_context_drop(const float* c, int B, int ncf, float p_drop, unsigned long long seed, unsigned int sub,
                      const int* sub_dev, float* c_out, int* keep, void* stream);

@@ -6,7 +6,8 @@
     (each at most 2^-24 relative to a value no larger than 2 max(|p|, |ema|) resp. max(|p|, |ema|)), the decay held as
     fp32 (1 - decay) adds one more 2^-24 of (1 - decay) |p - ema|, and the error carried in from earlier steps is
     multiplied by the decay (< 1): 4 * 2^-24 * max(|p|, |ema|) per step covers it, K steps add up to K times that.
-  * cdm_context_drop against cdm_philox_uniform on the same stream; a binomial count.
+  * cdm_context_drop against cdm_philox_uniform on the same stream (tests/test_gpu_rng.py holds that stream to a host
+    oracle); a binomial count; p_drop = 1 on a row whose u is exactly 1.0f.
   * Trainer: the defaults and the EMA trainer walk the same trajectory; graph replay == eager with both features on;
     an injected keep mask == a default trainer on the masked context; checkpoint -> new trainer continues bit for bit;
     ema_weights() swaps and restores; sampling inside it == sampling from a model loaded with ema_state_dict().
@@ -195,6 +196,24 @@ def test_context_drop_matches_the_uniform_stream(B, ncf):
     assert torch.equal(out, c0) and keep.all()
     out, keep, _ = _drop(c, 1.0, seed, sub, ctr)
     assert not out.any() and not keep.any()
+
+
+@pytest.mark.parametrize("ncf", [1, 6])
+def test_context_drop_p_one_drops_a_row_whose_u_is_one(ncf):
+    """u01 lies in (0, 1]: element 0 of the stream (seed 0, sub 1543363) is exactly 1.0f (tests/_rng_ref.py find_u_one),
+    so u < p_drop is false at p_drop = 1.  p_drop = 1 drops the row all the same; the next float below 1 is the plain
+    comparison and keeps it."""
+    seed, sub = 0, 1543363
+    ctr = torch.tensor([0], dtype=torch.int32, device="cuda")
+    c = torch.full((1, ncf), 2.5, device="cuda")
+    out, keep, u = _drop(c, 1.0, seed, sub, ctr)
+    assert u.view(torch.int32).item() == 0x3F800000, "the stream's first element is 1.0f"
+    assert keep.tolist() == [0]
+    assert torch.equal(out.view(torch.int32), torch.zeros_like(out, dtype=torch.int32)), "a +0 row"
+    out, keep, _ = _drop(c, 1.0, seed, sub - 5, torch.tensor([5], dtype=torch.int32, device="cuda"))   # sub + counter
+    assert keep.tolist() == [0] and not out.any()
+    out, keep, _ = _drop(c, 0.99999994, seed, sub, ctr)
+    assert keep.tolist() == [1] and torch.equal(out, c)
 
 
 def test_context_drop_counter_and_rate():
